@@ -11,22 +11,29 @@ and the per-Gaussian gradients ((59+C) floats each) are summed over RCCL inside 
 gradient's all-reduce starts inside the backward pass (dp.FeatureGradOverlap), the SH gradient's inside its last
 stage, row chunk by row chunk (dp.RowsGradOverlap).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5] [--no-cpu-baseline] [--comm-only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5] [--full] [--dump-outputs DIR] [--no-cpu-baseline] [--comm-only]
 
 `--gpus N` with N > 1 needs one process per GPU: started under torch.distributed.run it uses the ranks it is
 given; started plainly it re-launches itself under torch.distributed.run (same arguments) and relays that
 run's JSON line - it never reports a number measured on fewer GPUs than asked for.
 
-Rank 0 prints ONE JSON line.  What is measured where:
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up steps and an untimed pre-roll of min(2 K, 256) steps,
+times K steps and prints the headline:
   * `value` / `ms_per_step`: wall clock of exactly K steps between barrier + synchronize pairs, max over ranks
-    (the contract); `step_ms` adds the per-step distribution (median, p10, p90) from HIP events on the op's stream,
-    taken in the auxiliary run described below.
+    (the contract), with no event of the library's profiler inside them.
+  * `--dump-outputs DIR`: what the last timed step computed - colour, feature map, depth, radii and every leaf's
+    gradient - as float32 DIR/<name>.npy, at most 64 MB (a fixed, seeded sample of pixels and Gaussians where the
+    whole does not fit); the inputs are seeded, so two builds can be compared output for output.
+`--full` adds everything else, in runs of their own after the timed region (none of it is part of `value`):
   * `roofline`: the dominant kernel's ALGORITHMIC bytes per launch (restated in DESIGN.md)
     over its mean duration, measured live with HIP events recorded by the library around the two blend kernels
-    on the stream they run on, inside the timed region (library option profile = 2: four events per step).  The
-    full stage split (`stage_ms`) comes from an auxiliary run of the same K steps with an event at every stage
-    boundary (eleven per step, ~4 us of device time each) - it is not part of `value`.  `traffic` is null: HBM
-    counters cannot be read from inside this process; the separately profiled figure is quoted under `profiled`.
+    on the stream they run on, in a run of the same K steps (library option profile = 2: four events per step).
+    The full stage split (`stage_ms`) comes from an auxiliary run of the same K steps with an event at every stage
+    boundary (eleven per step, ~4 us of device time each); `step_ms` adds the per-step distribution (median, p10,
+    p90) from HIP events on the op's stream in that run.  `traffic` is null: HBM counters cannot be read from inside
+    this process; the separately profiled figure is quoted under `profiled`.
+  * `fp32_exact`: the same K steps with every contraction of the blend backward in exact fp32; `graph_replay` for c1;
+    `dp_breakdown` (N > 1) and `views_breakdown` (--views-per-iter): what the step is made of.
   * `cpu_baseline`: the scalar C++ oracle (a port, 1 core) on a bounded sample of the same workload;
     `cpu_reference_path_c1`: BASELINE.json config 1 - the PyTorch-CPU autograd restatement on all host cores
     next to the product on the GPU, both at c1 (SURVEY.md 8(d) "CPU reference timing").
@@ -290,8 +297,9 @@ def _stub_step(scene, dev, dist=None, n_views=1):
     return step, leaves
 
 
-def make_step(scene, dev, pool=4, dist=None, overlap=True):
-    """Returns (step(i), leaves): one forward+backward (+ gradient exchange) with the i-th upstream gradient set."""
+def make_step(scene, dev, pool=4, dist=None, overlap=True, last=None):
+    """Returns (step(i), leaves): one forward+backward (+ gradient exchange) with the i-th upstream gradient set.  A dict
+    `last` receives the forward's outputs of every step (`--dump-outputs`)."""
     import torch
     if STUB:
         return _stub_step(scene, dev, dist=dist)
@@ -318,8 +326,10 @@ def make_step(scene, dev, pool=4, dist=None, overlap=True):
     reduce_keys = ("means3D", "shs", "semantic_feature", "opacities", "scales", "rotations")   # 59 + C floats
 
     def fwd_bwd(i):
-        color, feat, _radii, depth = rasterizer(**leaves)
+        color, feat, radii, depth = rasterizer(**leaves)
         torch.autograd.backward([color, feat, depth], ups[i % pool])
+        if last is not None:
+            last.update(color=color, feature_map=feat, radii=radii, depth=depth)
 
     def step(i):
         for v in leaves.values():
@@ -335,13 +345,14 @@ def make_step(scene, dev, pool=4, dist=None, overlap=True):
     return step, leaves
 
 
-def make_step_views(scene, yaws, dev, pool=4, dist=None, overlap=True, pipelined=True):
+def make_step_views(scene, yaws, dev, pool=4, dist=None, overlap=True, pipelined=True, last=None):
     """Several views of the same Gaussians per rank and step (`--views-per-iter`): returns (step(i), leaves).  One step =
     forward+backward of every view in `yaws` (camera rotated about y by that many degrees) + the gradient exchange, through
     dp.dp_step_views: views alternate between two streams (view v + 1's preprocess / binning under view v's blend kernels),
     the feature gradient is accumulated in place across the views and - data parallel - reduced from inside the last view's
     backward pass.  pipelined=False: the same views strictly one after the other on one stream, one gradient tensor per view
-    (what dp.dp_step did with several views until round 3) - the comparison leg."""
+    (what dp.dp_step did with several views until round 3) - the comparison leg.  A dict `last` receives every view's forward
+    outputs (`--dump-outputs`)."""
     import torch
     if STUB:
         return _stub_step(scene, dev, dist=dist, n_views=len(yaws))
@@ -374,7 +385,9 @@ def make_step_views(scene, yaws, dev, pool=4, dist=None, overlap=True, pipelined
     state = {"i": 0}
 
     def forward(j):
-        color, feat, _radii, depth = rasterizers[j](**leaves)
+        color, feat, radii, depth = rasterizers[j](**leaves)
+        if last is not None:
+            last.update({f"color_view{j}": color, f"feature_map_view{j}": feat, f"radii_view{j}": radii, f"depth_view{j}": depth})
         return (color, feat, depth, j)
 
     def backward(h):
@@ -386,6 +399,45 @@ def make_step_views(scene, yaws, dev, pool=4, dist=None, overlap=True, pipelined
         dp.dp_step_views(forward, backward, sub, range(len(yaws)), overlap=overlap and pipelined, n_streams=2 if pipelined else 1,
                          accumulate=None if pipelined else False)
     return step, leaves
+
+
+PREROLL_MAX_STEPS = 256
+DUMP_BUDGET_BYTES = 60_000_000      # array data; with the .npy headers the files stay under 64 MB however counted
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir, images, per_gaussian):
+    """`--dump-outputs`: the arrays a caller of the timed step receives, as float32 `out_dir/<name>.npy`.  `images` maps names to
+    (channels, H, W) tensors of one size, `per_gaussian` to tensors with one row per Gaussian (None: not written).  All of it is
+    written whole when it fits in DUMP_BUDGET_BYTES; otherwise every image keeps the same seeded sample of pixels, sorted, written
+    as (channels, k), and every per-Gaussian array the same seeded sample of rows, each group within half of the budget."""
+    import numpy as np
+    import torch
+    images = {k: v.detach() for k, v in images.items() if v is not None}
+    per_gaussian = {k: v.detach() for k, v in per_gaussian.items() if v is not None}
+    arrays = {**images, **per_gaussian}
+    if 4 * sum(v.numel() for v in arrays.values()) > DUMP_BUDGET_BYTES:
+        half = DUMP_BUDGET_BYTES // 2
+
+        def sample_index(n, floats_per_item, salt):
+            k = min(n, max(1, half // (4 * max(1, floats_per_item))))
+            idx = np.sort(np.random.default_rng([DUMP_SAMPLE_SEED, salt]).choice(n, k, replace=False)) if k < n else np.arange(n)
+            return torch.from_numpy(idx.astype(np.int64))
+
+        if images:
+            H, W = next(iter(images.values())).shape[-2:]
+            idx = sample_index(H * W, sum(v.shape[0] for v in images.values()), 0)
+            for k, v in images.items():
+                arrays[k] = v.reshape(v.shape[0], H * W)[:, idx.to(v.device)]
+        if per_gaussian:
+            P = next(iter(per_gaussian.values())).shape[0]
+            idx = sample_index(P, sum(v.numel() // max(1, P) for v in per_gaussian.values()), 1)
+            for k, v in per_gaussian.items():
+                arrays[k] = v[idx.to(v.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.float().cpu().numpy())
+    return sorted(arrays)
 
 
 def config_label(P, W, H, C):
@@ -494,6 +546,9 @@ def densify_leg(args, dev):
         color, feat, radii, depth = rasterizer(**leaves)
         torch.autograd.backward([color, feat, depth], ups[i % 2])
         e1.record()
+        if args.dump_outputs and i == total - 1:
+            final = ({"color": color, "feature_map": feat, "depth": depth},
+                     {"radii": radii, **{f"grad_{k}": v.grad for k, v in leaves.items()}})
         for v in leaves.values():
             v.grad = None
         if i >= args.warmup:
@@ -501,6 +556,7 @@ def densify_leg(args, dev):
             p_list.append(int(leaves["means3D"].shape[0]))
     torch.cuda.synchronize()
     wall = time.perf_counter() - t_wall
+    dumped = dump_outputs(args.dump_outputs, *final) if args.dump_outputs else None
     step_ms = sorted(a.elapsed_time(b) for a, b in step_ms)
     dens = [a.elapsed_time(b) for a, b in dens_ms]
     pct = lambda q: step_ms[min(len(step_ms) - 1, int(q * len(step_ms)))]
@@ -520,6 +576,7 @@ def densify_leg(args, dev):
                              "includes": "densify.densify_and_prune + the activations of the new leaves (outside the step)"},
         "wall_ms_per_step_including_densification": 1e3 * wall / args.steps,
         "row_pool_reallocations": getattr(pool, "reallocations", None),
+        "dumped_outputs": dumped,
     }
     print(json.dumps(out), flush=True)
 
@@ -557,7 +614,15 @@ def main():
     ap.add_argument("--densify-every", type=int, default=0,
                     help="config c5 'densification on' (SURVEY.md 8d): every N steps 5 %% of the Gaussians are re-sampled through "
                          "densify.densify_and_prune between the timed iterations (N and the state buffers change)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: instance statistics, roofline and stage split (runs of their own), the "
+                         "exact-fp32 contraction, the c1 graph leg, the multi-rank / multi-view breakdowns and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (images, radii, every leaf's gradient) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed, seeded sample of pixels and Gaussians where the whole does not fit)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_reduced_c3:
         print(json.dumps(cpu_reference_path_c3_reduced()), flush=True)
@@ -628,11 +693,12 @@ def main():
     scene = make_scene(seed=0, yaw_deg=5.0 * rank * per_rank, **cfg_kw)
     P, C = scene["P"], scene["C"]
     W, H = scene["image_width"], scene["image_height"]
+    last = {} if args.dump_outputs else None        # the forward's outputs of the latest step (only kept when they are dumped)
     if V:
         yaws = [5.0 * (rank * per_rank + j) for j in range(per_rank)]
-        step, leaves = make_step_views(scene, yaws, dev, dist=dist, overlap=not args.no_overlap)
+        step, leaves = make_step_views(scene, yaws, dev, dist=dist, overlap=not args.no_overlap, last=last)
     else:
-        step, leaves = make_step(scene, dev, dist=dist, overlap=not args.no_overlap)
+        step, leaves = make_step(scene, dev, dist=dist, overlap=not args.no_overlap, last=last)
 
     def timed(n_steps, per_step_events):       # (`step` is looked up at call time)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_steps + 1)] if per_step_events and not STUB else None
@@ -661,6 +727,8 @@ def main():
         import dp
         if dist is None:
             raise SystemExit("--comm-only needs --gpus N > 1")
+        if args.dump_outputs:
+            raise SystemExit("--comm-only renders nothing: no --dump-outputs")
         for v in leaves.values():
             v.grad = torch.zeros_like(v)
         grads = {k: leaves[k].grad for k in ("means3D", "shs", "semantic_feature", "opacities", "scales", "rotations")}
@@ -727,37 +795,45 @@ def main():
         return
 
     stats = None
-    if rank == 0 and STUB:
+    if rank == 0 and args.full and STUB:
         stats = dict(Pv=P, N=4 * P, N_r=2 * P, tiles=12, bwd_evals=8 * P)
-    elif rank == 0:
+    elif rank == 0 and args.full:
         # N_r of SURVEY.md 8(d) is defined on the reference's (bounding-rectangle) instance lists
         _C.set_option("tile_cull", 0)
         stats = scene_stats(scene, dev)
         _C.set_option("tile_cull", 1)
         stats["bwd_evals"] = scene_stats(scene, dev)["bwd_evals"]      # of the lists the product walks
-    for i in range(args.warmup):
+    _C.set_option("profile", 0)
+    # the W warm-up steps, then an untimed pre-roll of min(2 K, PREROLL_MAX_STEPS) more: the GPU reaches its steady clock only
+    # after tens of ms of sustained work (c3, K = 20: 1.32 ms per timed step after W = 5 steps alone, 1.27 after the pre-roll)
+    preroll = min(2 * args.steps, PREROLL_MAX_STEPS)
+    for i in range(args.warmup + preroll):
         step(i)
-    # events-off reference run (same K steps): shows what the events of the timed region cost
-    _C.set_option("profile", 0)
-    el_plain, _ = timed(args.steps, per_step_events=False)
-    # THE timed region: HIP events around the two blend kernels (the roofline's kernel duration is measured HERE, on
-    # the op's stream)
-    _C.set_option("profile", 2)
-    # (the library creates its HIP events on first use and pools them: an untimed pass of the same K steps creates the 4 K events
-    # the timed region records, so that no hipEventCreate - one run in ten read 1.38 instead of 1.26 ms at c3, a 2.4 ms stall in
-    # its first profiled pass - falls inside it; counted in steps_run_before_the_timed_region)
-    timed(args.steps, per_step_events=False)
-    _C.profile_read()
-    _C.profile_reset()
+    # THE timed region: K steps, no event of the library's profiler in them
     elapsed, _ = timed(args.steps, per_step_events=False)
-    blend = {name: (ms, calls) for name, ms, calls in _C.profile_read()}
-    # auxiliary run of the same K steps with an event at every stage boundary (11 per step, ~4 us of device time each)
-    # and an event pair per step: the stage split and the per-step distribution; not part of `value`
-    _C.set_option("profile", 1)
-    _C.profile_reset()
-    el_stages, per_step = timed(args.steps, per_step_events=True)
-    prof = {name: (ms, calls) for name, ms, calls in _C.profile_read()}
-    _C.set_option("profile", 0)
+    # what was read and written stays valid until the next step: dump it now, before any other leg runs the step again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {k: v for k, v in last.items() if not k.startswith("radii")},
+                              {**{k: v for k, v in last.items() if k.startswith("radii")},
+                               **{f"grad_{k}": v.grad for k, v in leaves.items()}})
+    if args.full:
+        # HIP events around the two blend kernels (the roofline's kernel duration, on the op's stream) in a run of the same K steps
+        _C.set_option("profile", 2)
+        # (the library creates its HIP events on first use and pools them: an untimed pass of the same K steps creates the 4 K
+        # events the run records, so that no hipEventCreate - a 2.4 ms stall in the first profiled pass at c3 - falls inside it)
+        timed(args.steps, per_step_events=False)
+        _C.profile_read()
+        _C.profile_reset()
+        el_blend, _ = timed(args.steps, per_step_events=False)
+        blend = {name: (ms, calls) for name, ms, calls in _C.profile_read()}
+        # auxiliary run of the same K steps with an event at every stage boundary (11 per step, ~4 us of device time each)
+        # and an event pair per step: the stage split and the per-step distribution; not part of `value`
+        _C.set_option("profile", 1)
+        _C.profile_reset()
+        el_stages, per_step = timed(args.steps, per_step_events=True)
+        prof = {name: (ms, calls) for name, ms, calls in _C.profile_read()}
+        _C.set_option("profile", 0)
 
     # What ran: the blend backward's per-Gaussian sums go through bf16 matrix instructions (two-term operands, f32 accumulation)
     # when the pixel-lane kernel with its bf16 shape is selected - read from the library's options, not assumed.
@@ -769,7 +845,7 @@ def main():
         bwd_bf16_active = bool(_C.last_backward_contraction() == 1)
     bwd_hybrid = (not STUB) and _C.last_backward_contraction() == 2
     fp32_exact = None
-    if bwd_bf16_active and not V:
+    if args.full and bwd_bf16_active and not V:
         # the same K steps with every contraction of the blend backward on exact-fp32 matrix instructions (option bwd_bf16 = 0):
         # the figure to hold against a reference that computes in fp32 throughout
         _C.set_option("bwd_bf16", 0)
@@ -794,7 +870,7 @@ def main():
     # reads num_rendered back in the middle of its forward call (rasterizer_impl.cu:283).  One upstream-gradient set (the
     # graph's inputs are static); the frame's lists are checked against the provision after the timed replays.
     graph_replay = None
-    if not STUB and dist is None and not V and (args.graph or args.config == "c1"):
+    if not STUB and dist is None and not V and (args.graph or (args.full and args.config == "c1")):
         try:
             from graph_step import CapturedStep
             cs = CapturedStep(lambda: step(0)).capture()
@@ -846,7 +922,7 @@ def main():
                               "tile lists); compute only - the gradient exchange of a W-GPU split is the view-sharded step's"}
 
     views_breakdown = None
-    if V:
+    if args.full and V:
         # the same K steps with the views strictly one after the other (one stream, one gradient tensor per view), and one view
         # alone: what the pipelining and the in-place accumulation buy
         _step = step
@@ -867,7 +943,7 @@ def main():
                            "note": "sequential = the same views one after the other on one stream with a gradient tensor per view; "
                                    "one_view = a single view of this rank without any exchange"}
     dp_breakdown = None
-    if dist is not None and not V:
+    if args.full and dist is not None and not V:
         # the same K steps without the exchange, and the exchange alone on the gradients they left: what the scaling is made of
         import dp
         step_local, leaves_local = make_step(scene, dev, dist=None)
@@ -975,12 +1051,49 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         mpix = (V if V else world) * W * H / 1e6 / (elapsed / args.steps)
+        if args.valu or not mf:
+            blend_label = "vector pipe only (option feature_mfma = 0)"
+        elif C == 0:
+            blend_label = "RGB only: both blend kernels on the vector pipe (no feature contraction)"
+        else:
+            blend_label = ("forward: feature contraction on exact-fp32 matrix instructions; backward: " +
+                           ("every per-Gaussian sum on bf16 matrix instructions with two-term operands (f32 accumulation; option bwd_bf16 = 1; "
+                            "gradients within 1e-4 |g| + 1e-5 max|g| of the exact-fp32 contraction, tests/test_gpu_parity.py)"
+                            if bwd_bf16_active else "every per-Gaussian sum on exact-fp32 matrix instructions (option bwd_bf16 = 0)"))
+        dtype_label = "f32 (blend-backward sums: bf16 x 2-term products, f32 accumulate)" if bwd_bf16_active else "f32"
+        line = {
+            "metric": f"rendered Mpix/s of rasterizer fwd+bwd (train-step ms in ms_per_step), {config_label(P, W, H, C)}",
+            "value": mpix, "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if V else "weak", "vs_baseline": None,
+            "dtype": dtype_label, "data": "stub" if STUB else ("synthetic; REHEARSAL: all ranks share cuda:0, gloo as transport - not a measurement" if ONE_DEVICE and world > 1 else "synthetic"),
+            "blend_kernels": blend_label,
+            "options": {k: _C.get_option(k) for k in ("feature_mfma", "bwd_bf16", "bwd_bf16_max_ratio", "bwd_pl", "tile_cull", "sync_free")},
+            "blend_backward_contraction": "bf16 two-term" if bwd_bf16_active else
+                                          ("hybrid: bf16 feature / colour blocks, exact-fp32 moment block" if bwd_hybrid else "exact fp32"),
+            "graph_replay": graph_replay,
+            "band_split": band_split,
+            "config": {"workload": f"{args.config}: {P} Gaussians, {W}x{H}, SH degree {scene['sh_degree']}, feat_dim={C}, "
+                                   + (f"{V} views per step ({per_rank} per GPU, rotated 5 degrees apart, pipelined over two streams, "
+                                      f"gradients accumulated across the views)" if V else "one view per GPU")
+                                   + " (SURVEY.md 8d recipe, seed 0), fresh upstream gradients per step",
+                       "P": P,
+                       "parallelism": "single GPU" if world == 1 else
+                       f"view-sharded dp{world} + RCCL all-reduce of (59+C) floats per Gaussian"
+                       + ("" if args.no_overlap else ", feature and SH all-reduces started inside the backward pass")},
+            # the W warm-up steps and the pre-roll; every other run of the step (--full) comes after the K timed steps of `value`
+            "steps_run_before_the_timed_region": args.warmup + preroll,
+            "dumped_outputs": dumped,
+            "full": args.full,
+        }
+        if not args.full:
+            print(json.dumps(line), flush=True)
+    if rank == 0 and args.full:
         stage_ms = {k: v[0] / max(1, v[1]) for k, v in prof.items()}
         alg = algorithmic_bytes(P, stats["Pv"], stats["N"], stats["N_r"], W * H, stats["tiles"], C)
         kernel_stage = {"preprocess": "preprocess", "render_fwd": "render_fwd", "render_bwd": "render_bwd",
                         "preprocess_bwd": "preprocess_bwd"}
         dom = max(kernel_stage, key=lambda k: stage_ms.get(kernel_stage[k], 0.0))
-        if dom in blend:      # measured inside the timed region
+        if dom in blend:      # measured by the blend kernels' events, in the run right after the timed region
             dom_ms = blend[dom][0] / max(1, blend[dom][1])
         else:                 # a per-Gaussian kernel dominates (no such config so far): from the auxiliary run
             dom_ms = stage_ms.get(kernel_stage[dom], float("nan"))
@@ -1037,16 +1150,6 @@ def main():
                 pass
         per = sorted(per_step)
         pct = lambda q: per[min(len(per) - 1, int(q * len(per)))]
-        if args.valu or not mf:
-            blend_label = "vector pipe only (option feature_mfma = 0)"
-        elif C == 0:
-            blend_label = "RGB only: both blend kernels on the vector pipe (no feature contraction)"
-        else:
-            blend_label = ("forward: feature contraction on exact-fp32 matrix instructions; backward: " +
-                           ("every per-Gaussian sum on bf16 matrix instructions with two-term operands (f32 accumulation; option bwd_bf16 = 1; "
-                            "gradients within 1e-4 |g| + 1e-5 max|g| of the exact-fp32 contraction, tests/test_gpu_parity.py)"
-                            if bwd_bf16_active else "every per-Gaussian sum on exact-fp32 matrix instructions (option bwd_bf16 = 0)"))
-        dtype_label = "f32 (blend-backward sums: bf16 x 2-term products, f32 accumulate)" if bwd_bf16_active else "f32"
         views_here = per_rank if V else 1                      # views one rank renders per step
         alg_step = alg["total"] * views_here                   # algorithmic bytes ONE GPU moves per step
         alg_step_min = alg["total_min"] * views_here
@@ -1090,16 +1193,7 @@ def main():
                             "evaluations_source": "committed SQ_INSTS_VALU of this config / 26 vector instructions per (entry, wave) "
                                                   "(profiled.valu_issue; a separate run)"}
         out = {
-            "metric": f"rendered Mpix/s of rasterizer fwd+bwd (train-step ms in ms_per_step), {config_label(P, W, H, C)}",
-            "value": mpix, "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if V else "weak", "vs_baseline": None,
-            "dtype": dtype_label, "data": "stub" if STUB else ("synthetic; REHEARSAL: all ranks share cuda:0, gloo as transport - not a measurement" if ONE_DEVICE and world > 1 else "synthetic"),
-            "blend_kernels": blend_label,
-            "options": {k: _C.get_option(k) for k in ("feature_mfma", "bwd_bf16", "bwd_bf16_max_ratio", "bwd_pl", "tile_cull", "sync_free")},
-            "blend_backward_contraction": "bf16 two-term" if bwd_bf16_active else
-                                          ("hybrid: bf16 feature / colour blocks, exact-fp32 moment block" if bwd_hybrid else "exact fp32"),
-            "graph_replay": graph_replay,
-            "band_split": band_split,
+            **line,
             "ms_per_step_fp32_exact": fp32_exact["ms_per_step"] if fp32_exact else (ms_per_step if not bwd_bf16_active else None),
             "fp32_exact": ({**fp32_exact,
                             "value_mpix_s": world * W * H / 1e6 / (fp32_exact["ms_per_step"] * 1e-3),
@@ -1110,21 +1204,11 @@ def main():
                             "note": "the same K steps with option bwd_bf16 = 0: every contraction of the blend backward on exact-fp32 "
                                     "matrix instructions (bit-equal to an fmaf chain); the forward is exact fp32 in both"}
                            if fp32_exact else None),
-            "config": {"workload": f"{args.config}: {P} Gaussians, {W}x{H}, SH degree {scene['sh_degree']}, feat_dim={C}, "
-                                   + (f"{V} views per step ({per_rank} per GPU, rotated 5 degrees apart, pipelined over two streams, "
-                                      f"gradients accumulated across the views)" if V else "one view per GPU")
-                                   + " (SURVEY.md 8d recipe, seed 0), fresh upstream gradients per step",
-                       "P": P, "Pv": stats["Pv"], "N": stats["N"], "N_r": stats["N_r"],
-                       "parallelism": "single GPU" if world == 1 else
-                       f"view-sharded dp{world} + RCCL all-reduce of (59+C) floats per Gaussian"
-                       + ("" if args.no_overlap else ", feature and SH all-reduces started inside the backward pass")},
-            # order of the runs in this process: W warm-up steps, K steps without any event (reported as
-            # step_ms.ms_per_step_without_events), K untimed steps with the timed region's events (they create the library's
-            # event pool), THEN the K timed steps of `value`
-            "steps_run_before_the_timed_region": args.warmup + 2 * args.steps,
+            "config": {**line["config"], "Pv": stats["Pv"], "N": stats["N"], "N_r": stats["N_r"]},
             "step_ms": {"median": pct(0.5), "p10": pct(0.1), "p90": pct(0.9), "n": len(per),
                         "source": "HIP event pair per step on the op's stream, rank 0, in the auxiliary run with all stage events",
-                        "ms_per_step_without_events": 1e3 * el_plain / args.steps,
+                        "ms_per_step_without_events": ms_per_step,
+                        "ms_per_step_with_blend_events": 1e3 * el_blend / args.steps,
                         "ms_per_step_with_all_stage_events": 1e3 * el_stages / args.steps},
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "frac_of_achievable_6290": achieved / HBM_ACHIEVABLE_GBS,
@@ -1133,7 +1217,7 @@ def main():
                          "traffic": (profiled or {}).get(dom) if args.config == "c3" and not V else None,
                          "traffic_source": (profiled or {}).get("source") if args.config == "c3" and not V else None,
                          "algorithmic_bytes_per_launch": alg[dom], "kernel_ms": dom_ms,
-                         "kernel_ms_source": "HIP events around the kernel on the op's stream, inside the timed region",
+                         "kernel_ms_source": "HIP events around the kernel on the op's stream, in a run of the same K steps after the timed region",
                          "traffic_source_sha256_16": (profiled or {}).get("source_sha256_16") if args.config == "c3" and not V else None,
                          "note": "HBM is the roofline the contract names for this path; the kernel itself is bound by "
                                  "vector-instruction issue (an exponential, a reciprocal, three threshold tests and ~30 dependent operations "

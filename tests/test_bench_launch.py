@@ -22,7 +22,7 @@ def _run(*args, timeout=420):
 
 
 def test_two_ranks_relaunch_and_relay_one_line():
-    d = _run("--gpus", "2", "--steps", "2", "--warmup", "1")
+    d = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--full")
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["data"] == "stub"
     assert d["scaling"] == "weak" and d["higher_is_better"] is True and d["unit"] == "Mpix/s" and d["value"] > 0
     assert "dp2" in d["config"]["parallelism"] and "workload" in d["config"]
@@ -37,7 +37,7 @@ def test_two_ranks_relaunch_and_relay_one_line():
 
 
 def test_views_per_iter_line_is_strong_scaling_and_counts_views_per_gpu():
-    d = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--views-per-iter", "4")
+    d = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--views-per-iter", "4", "--full")
     assert d["n_gpus"] == 2 and d["scaling"] == "strong"
     assert d["views_breakdown"]["views_per_rank"] == 2
     w = d["roofline_whole_step"]
@@ -59,3 +59,53 @@ def test_asking_for_more_gpus_than_ranks_is_refused():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
     assert p.returncode != 0 and "WORLD_SIZE=1" in (p.stderr + p.stdout)
+
+
+def test_plain_line_is_the_headline_only(tmp_path):
+    """Without --full the line carries the headline and nothing that needs runs of its own; --steps is the timed step count."""
+    d = _run("--gpus", "1", "--steps", "3", "--warmup", "2")
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["full"] is False and d["steps_run_before_the_timed_region"] == 2 + 2 * 3
+    assert d["unit"] == "Mpix/s" and d["higher_is_better"] is True and d["value"] > 0 and d["ms_per_step"] > 0
+    assert "bf16" in d["dtype"] and d["metric"].startswith("rendered Mpix/s")
+    for k in ("roofline", "roofline_whole_step", "stage_ms", "step_ms", "fp32_exact", "dp_breakdown", "cpu_baseline"):
+        assert k not in d, k
+    assert d["dumped_outputs"] is None
+
+
+def test_dump_outputs_are_float_bounded_and_repeatable(tmp_path):
+    import numpy as np
+    runs = []
+    for n in range(2):
+        out = tmp_path / f"run{n}"
+        d = _run("--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out))
+        files = sorted(os.listdir(out))
+        assert files == sorted(f"{name}.npy" for name in d["dumped_outputs"]) and "grad_means3D.npy" in files
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10 ** 6
+        arrays = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        runs.append(arrays)
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+
+
+def test_dump_outputs_samples_what_does_not_fit(tmp_path):
+    """At the headline size the whole output is ~0.6 GB: the same seeded pixels / rows of every array, within the budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    P, C, H, W = 400_000, 32, 540, 960
+    images = {"color": torch.rand(3, H, W), "feature_map": torch.rand(C, H, W), "depth": torch.rand(1, H, W)}
+    rows = {"radii": torch.arange(P, dtype=torch.int32), "grad_shs": torch.rand(P, 16, 3), "grad_semantic_feature": torch.rand(P, 1, C)}
+    names = [bench.dump_outputs(str(tmp_path / f"d{n}"), images, rows) for n in range(2)]
+    assert names[0] == names[1] == sorted([*images, *rows])
+    total = sum(os.path.getsize(tmp_path / "d0" / f"{k}.npy") for k in names[0])
+    assert 0.9 * bench.DUMP_BUDGET_BYTES < total <= 64 * 10 ** 6
+    a = {k: np.load(tmp_path / "d0" / f"{k}.npy") for k in names[0]}
+    b = {k: np.load(tmp_path / "d1" / f"{k}.npy") for k in names[0]}
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    k_px = a["color"].shape[1]
+    assert a["feature_map"].shape == (C, k_px) and a["depth"].shape == (1, k_px) and k_px < H * W
+    idx = a["radii"].astype(np.int64)                    # radii = row index here: the sample is sorted and without repeats
+    assert np.all(np.diff(idx) > 0) and len(idx) < P
+    assert np.array_equal(a["grad_shs"], rows["grad_shs"].numpy()[idx])

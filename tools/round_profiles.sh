@@ -6,19 +6,19 @@ QUICK=${2:-}
 export TMPDIR=/tmp
 ROOT=$PWD; OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 # 1. bench lines: c3 full (driver contract), the other BASELINE configs single-GPU
-timeout 300 python bench.py > $OUT/${TAG}_bench_c3.json 2> $OUT/bench_c3.err
-for c in c1 c2 c4 c5; do timeout 200 python bench.py --config $c --no-cpu-baseline --steps 20 --warmup 5 > $OUT/${TAG}_bench_$c.json 2> $OUT/bench_$c.err; done
+timeout 300 python bench.py --full > $OUT/${TAG}_bench_c3.json 2> $OUT/bench_c3.err
+for c in c1 c2 c4 c5; do timeout 200 python bench.py --full --config $c --no-cpu-baseline --steps 20 --warmup 5 > $OUT/${TAG}_bench_$c.json 2> $OUT/bench_$c.err; done
 # 1a'. round 6: the step replayed from a HIP graph at c2 / c3 (the c1 line above carries its own graph_replay), one view as eight tile-row bands
-for c in c2 c3; do timeout 200 python bench.py --config $c --graph --no-cpu-baseline --steps 20 --warmup 5 > $OUT/${TAG}_bench_${c}_graph.json 2> $OUT/bench_${c}_graph.err; done
-for c in c3 c4 c5; do timeout 300 python bench.py --config $c --band-split 8 --no-cpu-baseline --steps 10 --warmup 3 > $OUT/${TAG}_bench_${c}_bands8.json 2> $OUT/bench_${c}_bands8.err; done
+for c in c2 c3; do timeout 200 python bench.py --full --config $c --graph --no-cpu-baseline --steps 20 --warmup 5 > $OUT/${TAG}_bench_${c}_graph.json 2> $OUT/bench_${c}_graph.err; done
+for c in c3 c4 c5; do timeout 300 python bench.py --full --config $c --band-split 8 --no-cpu-baseline --steps 10 --warmup 3 > $OUT/${TAG}_bench_${c}_bands8.json 2> $OUT/bench_${c}_bands8.err; done
 # 1b. the north-star-literal configuration (no matrix pipe anywhere), config c5 with densification on, several views per GPU
-timeout 200 python bench.py --no-cpu-baseline --valu > $OUT/${TAG}_bench_c3_valu.json 2> $OUT/bench_c3_valu.err
+timeout 200 python bench.py --full --no-cpu-baseline --valu > $OUT/${TAG}_bench_c3_valu.json 2> $OUT/bench_c3_valu.err
 timeout 300 python bench.py --config c5 --densify-every 5 --steps 40 --warmup 10 > $OUT/${TAG}_bench_c5_densify.json 2> $OUT/bench_c5_densify.err
-timeout 300 python bench.py --config c4 --views-per-iter 8 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_c4_8views.json 2> $OUT/bench_c4_8views.err
-timeout 300 python bench.py --config c3 --views-per-iter 8 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_c3_8views.json 2> $OUT/bench_c3_8views.err
+timeout 300 python bench.py --full --config c4 --views-per-iter 8 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_c4_8views.json 2> $OUT/bench_c4_8views.err
+timeout 300 python bench.py --full --config c3 --views-per-iter 8 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_c3_8views.json 2> $OUT/bench_c3_8views.err
 # 1b'. the LSeg width of the reference's README (NUM_SEMANTIC_CHANNELS 512) on c4's 2M Gaussians, and the fp32 shape of the blend backward
-timeout 200 python bench.py --config c4 --feat-dim 512 --no-cpu-baseline --steps 20 --warmup 5 > $OUT/${TAG}_bench_c4_C512.json 2> $OUT/bench_c4_C512.err
-F3DGS_BWD_BF16=0 timeout 200 python bench.py --no-cpu-baseline --steps 20 --warmup 5 > $OUT/${TAG}_bench_c3_bwd_fp32.json 2> $OUT/bench_c3_bwd_fp32.err
+timeout 200 python bench.py --full --config c4 --feat-dim 512 --no-cpu-baseline --steps 20 --warmup 5 > $OUT/${TAG}_bench_c4_C512.json 2> $OUT/bench_c4_C512.err
+F3DGS_BWD_BF16=0 timeout 200 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $OUT/${TAG}_bench_c3_bwd_fp32.json 2> $OUT/bench_c3_bwd_fp32.err
 timeout 200 python tools/adam_bench.py > $OUT/${TAG}_adam.txt 2>&1
 timeout 200 python tools/adam_bench.py 5000000 128 >> $OUT/${TAG}_adam.txt 2>&1
 timeout 200 python tools/feature_loss_bench.py > $OUT/${TAG}_feature_loss.txt 2>&1
@@ -39,7 +39,7 @@ timeout 600 python -m pytest tests/test_gpu_vs_ref.py -q -s -k "full_size or eig
 fi
 # 2. kernel trace of the SAME command as the bench (rocprofv3 --kernel-trace --stats)
 cd /tmp
-F3DGS_BENCH_NO_UBENCH=1 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/kt --output-format csv -- python $ROOT/bench.py --no-cpu-baseline > $OUT/kt_bench.json 2> $OUT/kt.err
+F3DGS_BENCH_NO_UBENCH=1 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/kt --output-format csv -- python $ROOT/bench.py --full --no-cpu-baseline > $OUT/kt_bench.json 2> $OUT/kt.err
 cd $ROOT
 python tools/rocprof_summary.py $OUT/kt $OUT/${TAG}_kernel_trace_c3.md
 # 3. counters, separate passes (no tracing in the same run)
