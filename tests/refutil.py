@@ -56,16 +56,22 @@ def product_module():
 
 
 def device_inputs(scene: dict, C_module: int, dev="cuda:0", precomp_color=False, precomp_cov=False) -> dict:
-    """Device tensors for one call.  When the module's baked-in feature width differs from the scene's
-    (RGB-only scene against a reference built with C = 3), a zero feature tensor of the module's width is used."""
+    """Device tensors for one call.  When the module's baked-in feature width is wider than the scene's (a ragged C against
+    the reference built with the next width up; an RGB-only scene against C = 3), the scene's C feature and upstream channels
+    come first and the rest, up to the module's width, are zero: zero channels change nothing in the first C channels or in any
+    geometric sum."""
     t = lambda x: x.to(dev).contiguous()
     e = torch.Tensor([])
-    P = scene["P"]
-    if scene["C"] == C_module:
+    P, C = scene["P"], scene["C"]
+    if C == C_module:
         feat, dfeat = t(scene["semantic_feature"]), t(scene["dL_dfeature"])
     else:
+        assert C < C_module, f"a {C}-channel scene does not fit a module of {C_module} channels"
         feat = torch.zeros(P, 1, C_module, device=dev)
         dfeat = torch.zeros(C_module, scene["image_height"], scene["image_width"], device=dev)
+        if C:
+            feat[:, :, :C] = t(scene["semantic_feature"])
+            dfeat[:C] = t(scene["dL_dfeature"])
     return dict(bg=t(scene["bg"]), means3D=t(scene["means3D"]), opacities=t(scene["opacities"]),
                 semantic_feature=feat,
                 colors_precomp=t(scene["colors_precomp"]) if precomp_color else e,

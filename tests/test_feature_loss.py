@@ -147,6 +147,8 @@ LOWRES_CASES = [
     (32, 200, 120, 120, 200, 0, False, 1.0),       # identity resize: every pixel is a sample
     (32, 200, 120, 87, 143, 0, True, 1.0),         # ~1.4x reduction: rows / columns with two samples; dense gradient added
     (40, 96, 64, 1, 1, 0, False, 1.0),             # one output pixel (scale 0): only source pixel (0, 0) is sampled
+    (33, 160, 96, 53, 80, 0, False, 1.0),          # ragged C: a one-channel later window
+    (161, 113, 75, 38, 57, 0, False, 1.0),         # ragged C: a 128-channel kernel8 window, then a one-channel window
 ]
 
 

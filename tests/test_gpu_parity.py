@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import ROOT, grad_report, precompute_optionals, run_hip, run_oracle
+from util import ROOT, _strict_compare, grad_report, precompute_optionals, run_hip, run_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -110,53 +110,6 @@ CASES = [
     dict(seed=11, P=4000, W=160, H=96, C=8, precomp_cov=True),
     dict(seed=12, P=2500, W=64, H=64, C=4, big=True),                # dense: early termination everywhere
 ]
-
-
-def _strict_compare(scene, pc=False, pv=False):
-    """HIP path vs the C++ oracle with the north-star bars: outputs <= 1e-4 abs, gradients <= 1e-3 rel
-    (`|err| <= 1e-3 |g| + 1e-5 max|g|` for EVERY element and max err <= 1e-3 max|g|), after the pixels PROVEN to be
-    threshold flips (refutil.flip_pixels: n_contrib / final-T evidence from both implementations) have been
-    counted, bounded and removed exactly by zeroing their upstream gradients on both sides."""
-    import refutil as ru
-    from util import set_option
-    W, H = scene["image_width"], scene["image_height"]
-    npix = W * H
-    o, want, _ = run_oracle(scene, pc, pv, backward=False)
-    old = set_option("tile_cull", 0)      # n_contrib is a list position: comparable only on the reference's lists
-    try:
-        d = ru.device_inputs(scene, scene["C"], "cuda:0", pc, pv)
-        f0 = ru.raw_forward(ru.product_module(), scene, d)
-        img_prod = ru.product_image_state(scene, f0)
-    finally:
-        set_option("tile_cull", old)
-    flips = ru.flip_pixels(dict(n_contrib=o.read("n_contrib"), final_T=o.read("final_T")), img_prod)
-    nflip = int(flips.sum())
-    assert nflip <= max(2, npix // 10000), f"{nflip} threshold-flip pixels"
-    ok = ~flips
-    masked = dict(scene)
-    keep = torch.from_numpy(ok.reshape(1, H, W))
-    for k in ("dL_dcolor", "dL_dfeature", "dL_ddepth"):
-        masked[k] = scene[k] * keep
-    got, got_g = run_hip(masked, pc, pv)
-    want_g = o.backward(masked["dL_dcolor"], masked["dL_dfeature"], masked["dL_ddepth"])
-    assert np.array_equal(got["radii"], want["radii"])
-    for k in ("color", "feature_map", "depth"):
-        if want[k].size == 0:
-            assert got[k].shape == want[k].shape
-            continue
-        err = np.abs(got[k] - want[k]).reshape(want[k].shape[0], -1).max(0)
-        assert err[ok].max() <= 1e-4, f"{k}: max abs err {err[ok].max():.3e} outside the {nflip} flip pixels"
-    names = {"dL_dmeans3D", "dL_dmeans2D", "dL_dsemantic_feature", "dL_dopacity"}
-    names |= {"dL_dcolors"} if pc else {"dL_dsh"}
-    names |= {"dL_dcov3D"} if pv else {"dL_dscales", "dL_drotations"}
-    for k in sorted(names):
-        w = want_g[k]
-        if w.size == 0:
-            continue
-        mx, worst = ru.grad_errors(got_g[k], w)
-        assert mx <= 1e-3, f"{k}: max err / max|g| = {mx:.2e}"
-        assert worst <= 1.0, f"{k}: worst element {worst:.2f}x outside 1e-3*|g| + 1e-5*max|g|"
-    return nflip
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items() if k != "bg"))

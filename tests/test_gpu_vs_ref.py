@@ -86,8 +86,9 @@ class _Side:
         return ru.ref_geometry_state(self.f, P, self.C_mod, want={"tiles_touched"})["tiles_touched"]
 
 
-def _forward_stats(A: _Side, B: _Side, same_width: bool):
-    """B against A: integer artefacts, flips, per-plane errors at the non-flip pixels, the pixels above the strict bars."""
+def _forward_stats(A: _Side, B: _Side, C: int):
+    """B against A: integer artefacts, flips, per-plane errors at the non-flip pixels, the pixels above the strict bars.  The
+    feature maps are compared in their first C channels (the scene's: a wider module's padded channels are zero)."""
     sc = A.scene
     W, H = sc["image_width"], sc["image_height"]
     st = {}
@@ -105,8 +106,8 @@ def _forward_stats(A: _Side, B: _Side, same_width: bool):
     errs = {}
     for i, k in ((1, "color"), (2, "feature"), (3, "depth")):
         a, b = A.f[i], B.f[i]
-        if k == "feature" and not same_width:
-            continue
+        if k == "feature":
+            a, b = a[:C], b[:C]
         assert a.shape == b.shape, (k, a.shape, b.shape)
         if a.numel() == 0:
             continue
@@ -123,12 +124,21 @@ def _forward_stats(A: _Side, B: _Side, same_width: bool):
     return st, flips, over
 
 
+def _first_channels(g: dict, C: int) -> dict:
+    """The feature gradient of a module wider than the scene in its first C channels; its padded columns must be zero."""
+    f = g["dL_dsemantic_feature"]
+    if f.shape[-1] > C:
+        assert not bool(f[..., C:].any()), "gradient in the zero-padded feature channels"
+        g = dict(g, dL_dsemantic_feature=f[..., :C])
+    return g
+
+
 def _backward_stats(A: _Side, B: _Side, over, names, self_noise=False):
     sc = A.scene
-    W, H = sc["image_width"], sc["image_height"]
+    W, H, C = sc["image_width"], sc["image_height"], sc["C"]
     keep = torch.from_numpy((~over).reshape(1, H, W)).to(DEV)
-    gA, gB = A.backward(keep), B.backward(keep)
-    gA2 = A.backward(keep) if self_noise else None      # the reference's own atomics noise (a second run of the same call)
+    gA, gB = _first_channels(A.backward(keep), C), _first_channels(B.backward(keep), C)
+    gA2 = _first_channels(A.backward(keep), C) if self_noise else None      # the reference's own atomics noise (a second run of the same call)
     st = {}
     for k in sorted(names):
         a, b = gA[k], gB[k]
@@ -141,7 +151,7 @@ def _backward_stats(A: _Side, B: _Side, over, names, self_noise=False):
     return st, gA, gB
 
 
-def _adjudicate(A: _Side, B: _Side, over, pc, pv, same_width, max_pixels=600):
+def _adjudicate(A: _Side, B: _Side, over, pc, pv, C, max_pixels=600):
     """fp64 verdict on the pixels of `over` (B = the product).  Returns counts; asserts every adjudicated pixel."""
     sc = A.scene
     W = sc["image_width"]
@@ -154,8 +164,8 @@ def _adjudicate(A: _Side, B: _Side, over, pc, pv, same_width, max_pixels=600):
 
     def take(S):
         v = dict(color=S.f[1][:, ys, xs].t().cpu().numpy(), depth=S.f[3][0, ys, xs].cpu().numpy(), final_T=S.img["final_T"][sel])
-        if same_width and S.f[2].numel():
-            v["feature"] = S.f[2][:, ys, xs].t().cpu().numpy()
+        if C and S.f[2].numel():
+            v["feature"] = S.f[2][:C, ys, xs].t().cpu().numpy()
         return v
     pv_, rv_ = take(B), take(A)
     bars = {k: v for k, v in STRICT_BARS.items() if k in pv_}
@@ -251,15 +261,20 @@ def _adjudicate_gradients(scene, ref_side, over, gst, g_ref, g_prod, pc, pv, max
     return dict(gaussians=int(len(ids)), tensors=n_el, mode=mode, product_worst_bounds_from_fp64=worst_p, reference_worst_bounds_from_fp64=worst_r)
 
 
-def _grad_names(pc, pv, same_width):
+def _grad_names(pc, pv, C):
     # dL_dcolors (gradient w.r.t. the per-Gaussian RGB) is returned in SH mode too (rasterize_points.cu:199)
     # dL_dcov3D (the cov2D stage's output, rasterize_points.cu:199) is returned whether the covariances were given or not
     names = {"dL_dmeans3D", "dL_dmeans2D", "dL_dopacity", "dL_dcolors", "dL_dcov3D"}
     names |= set() if pc else {"dL_dsh"}
     names |= set() if pv else {"dL_dscales", "dL_drotations"}
-    if same_width:
+    if C:
         names |= {"dL_dsemantic_feature"}
     return names
+
+
+def _padded_channels_are_zero(side: _Side, C: int):
+    """A module wider than the scene renders its zero-padded feature channels as zero."""
+    assert not bool(side.f[2][C:].any()), "feature map nonzero in the zero-padded channels"
 
 
 def _compare(scene, C_ref, pc=False, pv=False, check_state=True, self_noise=True, return_grads=False, against_default=True,
@@ -267,15 +282,15 @@ def _compare(scene, C_ref, pc=False, pv=False, check_state=True, self_noise=True
     """The three-way comparison of the module docstring; returns a dict of measured numbers (also asserted)."""
     W, H, P, C = scene["image_width"], scene["image_height"], scene["P"], scene["C"]
     npix = W * H
-    same = C == C_ref
-    names = _grad_names(pc, pv, same)
+    names = _grad_names(pc, pv, C)
     budget = flip_budget_for(npix)
     prod = _Side("prod", scene, C, pc, pv)
     strict = _Side("ref", scene, C_ref, pc, pv, strict=True)
+    _padded_channels_are_zero(strict, C)
     stats = {}
 
     # ---- 1. product vs the STRICT build: the bars as the north-star states them
-    st, flips, over = _forward_stats(strict, prod, same)
+    st, flips, over = _forward_stats(strict, prod, C)
     assert st["radii_mismatch"] == 0, f"{st['radii_mismatch']} radii differ from the strict reference build"
     assert st["num_rendered_diff"] == 0
     vis = prod.f[4].cpu().numpy() > 0            # (the reference leaves tiles_touched of culled Gaussians unwritten)
@@ -283,7 +298,7 @@ def _compare(scene, C_ref, pc=False, pv=False, check_state=True, self_noise=True
     assert st["flip_pixels"] <= budget, f"{st['flip_pixels']} threshold-flip pixels (budget {budget})"
     assert st["over_bar_pixels"] <= budget, f"{st['over_bar_pixels']} pixels above a bar (budget {budget})"
     assert st["n_contrib_equal_off_flips"]
-    st["adjudication"] = _adjudicate(strict, prod, over, pc, pv, same)       # every pixel above a bar, flip or not
+    st["adjudication"] = _adjudicate(strict, prod, over, pc, pv, C)       # every pixel above a bar, flip or not
     gst, g_ref, g_prod = _backward_stats(strict, prod, over, names, self_noise)
     st["gradient_adjudication"] = _adjudicate_gradients(scene, strict, over, gst, g_ref, g_prod, pc, pv, max_adjudicated, harsh)
     st["grads"] = gst
@@ -315,8 +330,9 @@ def _compare(scene, C_ref, pc=False, pv=False, check_state=True, self_noise=True
     # ---- 2. + 3. against the DEFAULT (FMA-contracted) build: the product, and the strict build of the same sources
     if against_default:
         dflt = _Side("ref", scene, C_ref, pc, pv, strict=False)
-        st_p, _f, over_p = _forward_stats(dflt, prod, same)
-        st_s, _f, over_s = _forward_stats(dflt, strict, same)
+        _padded_channels_are_zero(dflt, C)
+        st_p, _f, over_p = _forward_stats(dflt, prod, C)
+        st_s, _f, over_s = _forward_stats(dflt, strict, C)
         # a radius is ceil(3 sqrt(lambda_max)) (forward.cu:232): a last-bit difference in lambda can move a value sitting on an
         # integer across it - by one, for at most one Gaussian in 250k; num_rendered follows the rectangles
         gx, gy = (W + 15) // 16, (H + 15) // 16
@@ -374,6 +390,13 @@ CASES = [
     dict(id="C512-LSeg", seed=20, P=3000, W=160, H=96, C=512),
     dict(id="C512-LSeg-ragged-depthgrad", seed=21, P=2500, W=113, H=75, C=512, depth=True),
     dict(id="C512-1080p-120k", seed=22, P=120000, W=1920, H=1080, C=512, lo=0.003, hi=0.03),
+    # ragged widths against the next reference width up, its extra channels zero (refutil.device_inputs): a one-channel later
+    # window of the blend backward, a 33-channel later forward window behind a kernel8 backward window, a 3-channel forward
+    # window, a 97-channel kernel8 window
+    dict(id="C33-in-C64-1080p-100k", seed=34, P=100000, W=1920, H=1080, C=33, Cref=64, lo=0.003, hi=0.03),
+    dict(id="C161-in-C256-1080p-50k", seed=35, P=50000, W=1920, H=1080, C=161, Cref=256, lo=0.003, hi=0.03),
+    dict(id="C131-in-C256-ragged-depthgrad", seed=36, P=4000, W=113, H=75, C=131, Cref=256, depth=True),
+    dict(id="C257-in-C512", seed=37, P=3000, W=160, H=96, C=257, Cref=512),
     # inputs outside the synthetic family (tests/util.py: harsh_scene)
     # (against the strict build only: on ill-conditioned inputs the reference's two builds are noise against each other)
     dict(id="heavy-tail-1080p-C32", seed=23, P=450000, W=1920, H=1080, C=32, harsh="heavy_tail_round", noise=False, dflt=False),
@@ -422,7 +445,7 @@ def _needle_errors(scene, case, strict, g_ref, over):
     PRODUCT in units of the north-star bound against the fp64 gradient (full fp64 backward over the tiles of every Gaussian
     above the bound, as the main test adjudicates them) - and the reference's on the same Gaussians."""
     P, C = scene["P"], scene["C"]
-    names = _grad_names(False, False, True)
+    names = _grad_names(False, False, C)
     prod = _Side("prod", scene, C, False, False)
     keep = torch.from_numpy((~over).reshape(1, scene["image_height"], scene["image_width"])).to(DEV)
     g_prod = prod.backward(keep)
@@ -473,7 +496,7 @@ def test_needles_take_the_exact_contraction_and_the_allowance_is_not_the_splits(
     C = scene["C"]
     strict = _Side("ref", scene, C, False, False, strict=True)
     probe = _Side("prod", scene, C, False, False)
-    _st, _flips, over = _forward_stats(strict, probe, True)
+    _st, _flips, over = _forward_stats(strict, probe, C)
     keep = torch.from_numpy((~over).reshape(1, scene["image_height"], scene["image_width"])).to(DEV)
     g_ref = strict.backward(keep)
     del probe
@@ -531,12 +554,12 @@ def test_non_finite_positions_vanish_as_in_the_reference():
     assert int((prod.f[4][bad.to(DEV)] != 0).sum()) == 0
     for i in (1, 2, 3):
         assert bool(torch.isfinite(prod.f[i]).all()) and bool(torch.isfinite(ref.f[i]).all())
-    st, flips, over = _forward_stats(ref, prod, True)
+    st, flips, over = _forward_stats(ref, prod, C)
     assert st["flip_pixels"] <= flip_budget_for(320 * 200) and st["over_bar_pixels"] <= flip_budget_for(320 * 200), st
     keep = torch.from_numpy((~over).reshape(1, 200, 320)).to(DEV)
     g_ref, g_prod = ref.backward(keep), prod.backward(keep)
     good = (~bad).to(DEV)
-    for k in sorted(_grad_names(False, False, True)):
+    for k in sorted(_grad_names(False, False, C)):
         a, b = g_ref[k], g_prod[k]
         assert a.shape == b.shape
         assert bool(torch.isfinite(b[good]).all()), k
