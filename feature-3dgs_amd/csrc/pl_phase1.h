@@ -29,10 +29,87 @@ struct PlRec {
     float4 q2;   // red, green, blue, depth
 };
 
-// BF tile layout (32 KB per tile): quadrant q at byte 8192 q; term t (0: w high, 1: w middle, 2: s high, 3: s middle) at
-// + 2048 t; row (entry) i at + 128 i; the row's eight 16-byte units = the eight pixel rows of the quadrant, unit y stored at
-// slot y ^ (i >> 1); pixel x of the row at + 2 x.
-constexpr int BF_QUAD = 8192, BF_TERM = 2048, BF_ROWB = 128;
+// BF tile layout (32 KB per tile, aliased on PlShared::wt / ::st): quadrant q at byte BF_QUAD q, term t (0: w high, 1: w middle,
+// 2: s high, 3: s middle) at + BF_TERM t; each (quadrant, term) image is [64 pixels][16 entries x bf16], 32 bytes per pixel row:
+// the entries of one pixel are contiguous, so a lane of phase 1 (one pixel) stores an entry pair of a term with ONE ds_write_b32,
+// and phase 2 reads its A fragments (entry = M, pixel = K) transposed with ds_read_b64_tr_b16.  The 8-byte slot of pixel p's
+// entries 4 c .. 4 c + 3 is bf_slot(p, c): pixel row p ^ (4 bit3(p)) - the two 32-lane halves of a transposed read take rows 8
+// apart, which would meet on the same banks - and slot c ^ bits 2..3 of p, which spreads a store's 32 lanes over all 16 slot
+// positions of the 128-byte ds_write bank row (2-way, the least a 32-lane ds_write_b32 can be).  Proven below.
+constexpr int BF_QUAD = 8192, BF_TERM = 2048, BF_SPAN = 1024;     // BF_SPAN: the 32 pixels (K = 32) of one matrix instruction
+
+// byte offset, inside a (quadrant, term) image, of pixel p's entries 4 c .. 4 c + 3 (p = 8 y + x of the quadrant, lane of phase 1)
+constexpr uint32_t bf_slot(uint32_t p, uint32_t c) { return 32u * (p ^ (((p >> 3) & 1u) << 2)) + 8u * (c ^ ((p >> 2) & 3u)); }
+// phase 1: lane p's slot of entries 0..3 in quadrant q's tiles; the pair m (entries 2 m, 2 m + 1) of a term is at ^ 4 m
+constexpr uint32_t bf_store_base(uint32_t q, uint32_t p) { return q * (uint32_t)BF_QUAD + bf_slot(p, 0); }
+// phase 2: the address lane l supplies to read r (0, 1) of a 16x16x32 A fragment of span 0 (span ks at + BF_SPAN ks).  Lane
+// 4 i + c of the 16-lane group g gives row i of the group's 4-pixel block, entries 4 c .. 4 c + 3; lane e of the group receives
+// entry e at the block's four pixels 8 g + 4 r + i, i.e. the fragment's K slots 8 g + j (j = 4 r + i) hold the pixels 8 g + j
+// (32 ks + 8 g + j in the quadrant) - the order of the resident B operand.  Read 1 is read 0 ^ 0x88.
+constexpr uint32_t bf_tr_ofs(uint32_t l, uint32_t r) { return bf_slot(8u * (l >> 4) + 4u * r + ((l & 15u) >> 2), l & 3u); }
+
+namespace bf_layout_proof {
+constexpr uint32_t BF_IMG = 64 * 32;
+// every (pixel, entry) element of an image written exactly once, and the store address form of phase 1
+constexpr bool stores_cover_the_image() {
+    int hits[BF_IMG / 2] = {};
+    for (uint32_t p = 0; p < 64; p++)
+        for (uint32_t e = 0; e < 16; e++) {
+            const uint32_t a = (bf_store_base(0, p) ^ (4u * (e >> 1))) + 2u * (e & 1u);
+            if (a != bf_slot(p, e >> 2) + 2u * (e & 3u) || a >= BF_IMG) return false;
+            if (bf_store_base(3, p) - bf_store_base(0, p) != 3u * BF_QUAD) return false;
+            hits[a / 2]++;
+        }
+    for (uint32_t i = 0; i < BF_IMG / 2; i++) if (hits[i] != 1) return false;
+    return true;
+}
+// ds_write_b32 of an entry pair: bank (a / 4) mod 32, at most two lanes of a 32-lane half on one bank
+constexpr bool stores_at_most_2way() {
+    for (uint32_t m = 0; m < 8; m++)
+        for (uint32_t h = 0; h < 2; h++) {
+            int n[32] = {};
+            for (uint32_t p = 32 * h; p < 32 * h + 32; p++) n[((bf_store_base(0, p) ^ (4u * m)) / 4) % 32]++;
+            for (int b = 0; b < 32; b++) if (n[b] > 2) return false;
+        }
+    return true;
+}
+// ds_read_b64_tr_b16: 8-byte aligned, bank (a / 4) mod 64, the two dwords of the 32 lanes of a half on 64 different banks
+constexpr bool reads_aligned_and_conflict_free() {
+    for (uint32_t ks = 0; ks < 2; ks++)
+        for (uint32_t r = 0; r < 2; r++)
+            for (uint32_t h = 0; h < 2; h++) {
+                int n[64] = {};
+                for (uint32_t l = 32 * h; l < 32 * h + 32; l++) {
+                    const uint32_t a = BF_SPAN * ks + bf_tr_ofs(l, r);
+                    if (a % 8 != 0 || bf_tr_ofs(l, 1) != (bf_tr_ofs(l, 0) ^ 0x88u)) return false;
+                    n[(a / 4) % 64]++; n[(a / 4 + 1) % 64]++;
+                }
+                for (int b = 0; b < 64; b++) if (n[b] != 1) return false;
+            }
+    return true;
+}
+// store -> read round trip: element j of lane l's fragment of span ks (the transposed read's gather: lane e of a 16-lane group
+// takes element e & 3 of what lane 4 i + (e >> 2) addressed, i = j & 3, in read j >> 2) is entry l & 15 at pixel 32 ks + 8 (l >> 4)
+// + j as phase 1 stored it, and the 2 x 64 x 8 fragment elements touch every element of the image once
+constexpr bool round_trip() {
+    int hits[BF_IMG / 2] = {};
+    for (uint32_t ks = 0; ks < 2; ks++)
+        for (uint32_t l = 0; l < 64; l++)
+            for (uint32_t j = 0; j < 8; j++) {
+                const uint32_t g = l >> 4, e = l & 15u, src = 16u * g + 4u * (j & 3u) + (e >> 2);
+                const uint32_t a = BF_SPAN * ks + bf_tr_ofs(src, j >> 2) + 2u * (e & 3u);
+                const uint32_t p = 32u * ks + 8u * g + j;
+                if (a != (bf_store_base(0, p) ^ (4u * (e >> 1))) + 2u * (e & 1u)) return false;
+                hits[a / 2]++;
+            }
+    for (uint32_t i = 0; i < BF_IMG / 2; i++) if (hits[i] != 1) return false;
+    return true;
+}
+static_assert(stores_cover_the_image(), "phase-1 stores: one store per (pixel, entry), inside the image");
+static_assert(stores_at_most_2way(), "phase-1 ds_write_b32: at most 2-way bank conflicts");
+static_assert(reads_aligned_and_conflict_free(), "ds_read_b64_tr_b16: 8-byte aligned and conflict-free per 32-lane half");
+static_assert(round_trip(), "A fragment = entry x (pixel 32 ks + 8 g + j): the K order of the resident B operand");
+}  // namespace bf_layout_proof
 
 __device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(p1_f32x2{lo, hi}, p1_bf16x2));
@@ -46,7 +123,8 @@ struct P1Pixel {
 };
 
 // Sixteen entries rc[0..15] (list positions pos_hi, pos_hi - 1, ...) against this lane's pixel.  T, S: transmittance and
-// "colour behind" carried along the walk.  tiles + sofs: this lane's slot in row 0 of the quadrant's w-high plane.
+// "colour behind" carried along the walk.  tiles + sofs: this lane's slot of entries 0..3 in the quadrant's w-high image
+// (sofs = bf_store_base(quadrant, lane)).
 // Returns the rows (bit e = entry e) that blended at some pixel of the wave.
 // NOLDS (tools/ubench/blend_stream.hip only): four records read once per chunk stand in for all sixteen (one extra vector
 // instruction per entry moves the mean) and the stores are dropped: the vector-pipe stream alone.
@@ -66,9 +144,10 @@ __device__ __forceinline__ uint32_t pl_phase1_bf16(const PlRec* rc, const P1Pixe
         unsigned long long m1, m2, m3;
     };
     Ent en[4];             // ring: entry e lives in en[e & 3]
-    float Tb = 0.f, nSf = 0.f, wv = 0.f, dLa = 0.f, sv = 0.f, rw = 0.f, rs = 0.f, w_even = 0.f;
-    uint32_t h = 0, hl = 0, hh = 0, m = 0;
-    (void)nSf; (void)dLa; (void)sv; (void)rs; (void)w_even; (void)hh;
+    // (the pair's even entry waits in w_even / s_even for its odd neighbour; rw, rs: the pair's middle w terms, rse, rso: of s)
+    float Tb = 0.f, nSf = 0.f, wv = 0.f, dLa = 0.f, sv = 0.f, rw = 0.f, rs = 0.f, w_even = 0.f, s_even = 0.f, rse = 0.f, rso = 0.f;
+    uint32_t h = 0, hl = 0, hh = 0, m = 0, hs = 0, ms = 0;
+    (void)nSf; (void)dLa; (void)sv; (void)rs; (void)w_even; (void)hh; (void)s_even; (void)rse; (void)rso; (void)hs; (void)ms;
 
     uint32_t sink = 0;
     (void)sink;
@@ -128,10 +207,13 @@ __device__ __forceinline__ uint32_t pl_phase1_bf16(const PlRec* rc, const P1Pixe
             default: break;
         }
     };
-    // stage C2: the recurrences of the walk, the two-term bf16 split, the stores
+    // stage C2: the recurrences of the walk; on the odd entry of a pair the two-term bf16 split of the pair and its stores.  Each
+    // v_cvt_pk_bf16_f32 converts one term of two entries (even entry in the low half), so a term of the pair leaves with one
+    // ds_write_b32 (see bf_slot).  The middle term is the residual of the rounded fp32 value, exact: w - hi(w).
     auto stage_c2 = [&](int k, int e) {
         Ent& x = en[e & 3];
-        char* const bp = tiles + (sofs ^ (uint32_t)(16 * (e >> 1))) + e * BF_ROWB;
+        char* const bp = tiles + (sofs ^ (uint32_t)(4 * (e >> 1)));       // this lane's pair e >> 1, term 0
+        const bool odd = e & 1;
         if constexpr (GEO) {
             switch (k) {
                 case 0: Tb = T * x.f; break;                              // transmittance in front of this splat
@@ -140,49 +222,51 @@ __device__ __forceinline__ uint32_t pl_phase1_bf16(const PlRec* rc, const P1Pixe
                 case 3: dLa = fmaf(Tb, x.qd, nSf); break;                 // dL/dalpha
                 case 4: S = fmaf(wv, x.qd, S); break;
                 case 5: sv = x.au * dLa; break;
-                case 6: h = pack_bf16(wv, S32 ? 0.f : sv); break;         // low half: w high term, high half: s high term
-                case 7: hl = h << 16; break;
-                case 8: if constexpr (!S32) hh = h & 0xFFFF0000u; break;
-                case 9: rw = fmaf(x.al, Tb, -__uint_as_float(hl)); break; // residual of the unrounded product
-                case 10: if constexpr (!S32) rs = fmaf(x.au, dLa, -__uint_as_float(hh)); break;
-                case 11: m = pack_bf16(rw, S32 ? 0.f : rs); break;
+                case 6:
+                    if (!odd) { w_even = wv; if constexpr (!S32) s_even = sv; }
+                    else { h = pack_bf16(w_even, wv); hl = h << 16; }
+                    break;
+                case 7: if (odd) { rw = w_even - __uint_as_float(hl); hh = h & 0xFFFF0000u; } break;
+                case 8: if (odd) { rs = wv - __uint_as_float(hh); if constexpr (!S32) hs = pack_bf16(s_even, sv); } break;
+                case 9: if constexpr (!S32) if (odd) { hl = hs << 16; hh = hs & 0xFFFF0000u; } break;
+                case 10: if constexpr (!S32) if (odd) { rse = s_even - __uint_as_float(hl); rso = sv - __uint_as_float(hh); } break;
+                case 11: if (odd) { m = pack_bf16(rw, rs); if constexpr (!S32) ms = pack_bf16(rse, rso); } break;
                 case 12:
                     if constexpr (S32) {
-                        *reinterpret_cast<uint16_t*>(bp) = (uint16_t)h;
-                        *reinterpret_cast<uint16_t*>(bp + BF_TERM) = (uint16_t)m;
+                        if (odd) {
+                            *reinterpret_cast<uint32_t*>(bp) = h;
+                            *reinterpret_cast<uint32_t*>(bp + BF_TERM) = m;
+                        }
                         *reinterpret_cast<float*>(s_tile + (s_ofs ^ (uint32_t)(16 * e))) = sv;
                     } else if constexpr (NOLDS) {
-                        asm volatile("" : "+v"(h), "+v"(m));      // (the values stay alive; nothing is stored)
-                        sink = h;
-                    } else {
-                        *reinterpret_cast<uint16_t*>(bp) = (uint16_t)h;
-                        *reinterpret_cast<uint16_t*>(bp + BF_TERM) = (uint16_t)m;
-                        *reinterpret_cast<uint16_t*>(bp + 2 * BF_TERM) = (uint16_t)(h >> 16);
-                        *reinterpret_cast<uint16_t*>(bp + 3 * BF_TERM) = (uint16_t)(m >> 16);
+                        if (odd) { asm volatile("" : "+v"(h), "+v"(m), "+v"(hs), "+v"(ms)); sink = h ^ hs; }
+                    } else if (odd) {
+                        *reinterpret_cast<uint32_t*>(bp) = h;
+                        *reinterpret_cast<uint32_t*>(bp + BF_TERM) = m;
+                        *reinterpret_cast<uint32_t*>(bp + 2 * BF_TERM) = hs;
+                        *reinterpret_cast<uint32_t*>(bp + 3 * BF_TERM) = ms;
                     }
                     T = Tb;
                     break;
                 default: break;
             }
         } else {
-            // later channel windows: the weight only; two entries share a conversion (rows e - 1 and e share their XOR term)
+            // later channel windows: the weight only
             switch (k) {
                 case 0: Tb = T * x.f; break;
                 case 2: wv = x.al * Tb; break;
-                case 6: if (e & 1) h = pack_bf16(w_even, wv); break;
-                case 7: if (e & 1) hl = h << 16; break;
-                case 8: if (e & 1) hh = h & 0xFFFF0000u; break;
-                case 9: if (e & 1) rw = w_even - __uint_as_float(hl); break;
-                case 10: if (e & 1) rs = wv - __uint_as_float(hh); break;
-                case 11: if (e & 1) m = pack_bf16(rw, rs); break;
+                case 6: if (odd) h = pack_bf16(w_even, wv); break;
+                case 7: if (odd) hl = h << 16; break;
+                case 8: if (odd) hh = h & 0xFFFF0000u; break;
+                case 9: if (odd) rw = w_even - __uint_as_float(hl); break;
+                case 10: if (odd) rs = wv - __uint_as_float(hh); break;
+                case 11: if (odd) m = pack_bf16(rw, rs); break;
                 case 12:
                     if constexpr (NOLDS) {
-                        if (e & 1) { asm volatile("" : "+v"(h), "+v"(m)); sink = h; } else w_even = wv;
-                    } else if (e & 1) {
-                        *reinterpret_cast<uint16_t*>(bp - BF_ROWB) = (uint16_t)h;
-                        *reinterpret_cast<uint16_t*>(bp - BF_ROWB + BF_TERM) = (uint16_t)m;
-                        *reinterpret_cast<uint16_t*>(bp) = (uint16_t)(h >> 16);
-                        *reinterpret_cast<uint16_t*>(bp + BF_TERM) = (uint16_t)(m >> 16);
+                        if (odd) { asm volatile("" : "+v"(h), "+v"(m)); sink = h; } else w_even = wv;
+                    } else if (odd) {
+                        *reinterpret_cast<uint32_t*>(bp) = h;
+                        *reinterpret_cast<uint32_t*>(bp + BF_TERM) = m;
                     } else {
                         w_even = wv;
                     }

@@ -47,6 +47,12 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef short i16x4 __attribute__((ext_vector_type(4)));
+// ds_read_b64_tr_b16 at an LDS address: per 16-lane group a 4 x 16 block of bf16 delivered transposed (pl_phase1.h, bf_tr_ofs)
+__device__ __forceinline__ u32x2 lds_read_tr16(const char* p) {
+    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(p)));
+}
 
 // ---- bf16 split operands (template parameter BF; option bwd_bf16) -------------------------------------------------------------
 // An fp32 matrix instruction occupies its SIMD for its whole duration (it excludes the vector instructions of the other
@@ -58,8 +64,8 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // tolerance is what allows the two-term split (the forward's 1e-4 ABSOLUTE bar on O(1) features would not).  The monomials of
 // the moment block (1, u, v, u^2, uv, v^2 with |u|, |v| <= 3.5 in steps of 1) have at most six significant bits: exact in bf16,
 // one term.  Per chunk a wave issues 24 (moment wave: 16) matrix instructions of 16 cycles instead of 64 of 32 cycles.
-// One v_cvt_pk_bf16_f32 converts two values (round to nearest even); the halves are stored with ds_write_b16 /
-// ds_write_b16_d16_hi as they stand.
+// One v_cvt_pk_bf16_f32 converts one term of two consecutive entries (round to nearest even); phase 1 stores it with one
+// ds_write_b32 into an image whose entries are contiguous per pixel, and phase 2 reads it transposed (ds_read_b64_tr_b16).
 // (lo, hi) -> packed high terms `h` and packed middle terms `m`
 __device__ __forceinline__ void split_bf16(float lo, float hi, uint32_t& h, uint32_t& m) {
     h = pack_bf16(lo, hi);
@@ -69,11 +75,9 @@ __device__ __forceinline__ f32x4 mfma_bf16(const uint32_t (&a)[4], const uint32_
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, u32x4{a[0], a[1], a[2], a[3]}),
                                                    __builtin_bit_cast(bf16x8, u32x4{b[0], b[1], b[2], b[3]}), c, 0, 0, 0);
 }
-// BF tile layout (aliases PlShared::wt and ::st, 32 KB; constants in pl_phase1.h): quadrant q at byte 8192 q; term t (0: w high,
-// 1: w middle, 2: s high, 3: s middle) at + 2048 t; row (entry) i at + 128 i; the row's eight 16-byte units = the eight pixel rows
-// of the quadrant, unit y stored at slot y ^ (i >> 1); pixel x of the row at + 2 x.  Operand lane (i, kg) of K span ks reads unit
-// 4 ks + kg of row i - sixteen bytes = the K slots 8 kg .. 8 kg + 7 - and the sixteen lanes of a ds_read_b128 service group meet
-// sixteen different 16-byte slots of the 256-byte bank row (two rows per bank row x eight slots).
+// BF tile layout (aliases PlShared::wt and ::st, 32 KB): pl_phase1.h, bf_slot.  Per quadrant and term a [64 pixels][16 entries]
+// bf16 image; operand lane (entry e, K group g) of span ks takes its eight K slots (pixels 32 ks + 8 g .. + 7) with two transposed
+// reads, each conflict-free per 32-lane half (static_asserts next to bf_slot).
 
 // Workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global access of the
 // wave - here the fire-and-forget atomics of the flush, microseconds under load - which nothing in the workgroup reads.
@@ -498,9 +502,9 @@ __device__ __forceinline__ void render_backward_pl_body(const BwdArgs& a) {
     const uint32_t wofs_b = (uint32_t)(((ccol >> 2) * PL_ROW + ((ccol >> 2) & 7) * 4 + (ccol & 3)) * 4);     // bytes, row 0
     char* const my_wt = reinterpret_cast<char*>(&L.wt[q][0]);
     constexpr int ST_OFS = 4 * PL_TILE;             // st[q] - wt[q], dwords
-    // BF: the bf16 tiles alias wt / st (32 KB); this lane's pixel in its quadrant's rows: unit ly (XOR-ed per row), element lx
+    // BF: the bf16 tiles alias wt / st (32 KB); this lane's (pixel's) slot of entries 0..3 in its quadrant's images
     char* const bf_tiles = reinterpret_cast<char*>(&L.wt[0][0]);
-    const uint32_t bf_sofs = (uint32_t)(q * BF_QUAD + ly * 16 + lx * 2);
+    const uint32_t bf_sofs = bf_store_base((uint32_t)q, (uint32_t)(8 * ly + lx));
         if (!PL_DEV_SKIP(32)) PL_PHASE_END(0);
 
     // ---- record loader (waves 0..2: one 16-byte third of every record; lane = entry, entry 0 = farthest back) -------
@@ -577,8 +581,6 @@ __device__ __forceinline__ void render_backward_pl_body(const BwdArgs& a) {
                     constexpr bool PREF = decltype(prefc)::value;
                     float4 n0[NE], n2[NE];
                     float2 n1[NE];
-                    float w_even = 0.f;       // BF, later windows: the even entry's weight waits for its odd neighbour
-                    (void)w_even;
                     if constexpr (PREF) {
 #pragma unroll
                         for (int k = 0; k < NE; k++) {
@@ -628,37 +630,12 @@ __device__ __forceinline__ void render_backward_pl_body(const BwdArgs& a) {
                         for (int k = 0; k < NE; k++) {
                             const float Tb = T * f[k];              // transmittance in front of this splat
                             const float wv = al[k] * Tb;
-                            if constexpr (BF) {
-                                // two bf16 terms per value; row e of the quadrant's tiles, this lane's pixel (see BF_QUAD)
-                                const int e = NE * p + k;
-                                char* const bp = bf_tiles + (bf_sofs ^ (uint32_t)(16 * (e >> 1))) + e * BF_ROWB;
-                                if constexpr (GEO) {
-                                    const float dL_dalpha = fmaf(Tb, qd[k], -(S * f[k]));
-                                    S = fmaf(wv, qd[k], S);
-                                    uint32_t h, m;
-                                    split_bf16(wv, au[k] * dL_dalpha, h, m);      // low halves: w, high halves: s
-                                    *reinterpret_cast<uint16_t*>(bp) = (uint16_t)h;
-                                    *reinterpret_cast<uint16_t*>(bp + BF_TERM) = (uint16_t)m;
-                                    *reinterpret_cast<uint16_t*>(bp + 2 * BF_TERM) = (uint16_t)(h >> 16);
-                                    *reinterpret_cast<uint16_t*>(bp + 3 * BF_TERM) = (uint16_t)(m >> 16);
-                                } else if ((e & 1) == 0) {
-                                    w_even = wv;                                     // converted together with the next entry's
-                                } else {
-                                    uint32_t h, m;
-                                    split_bf16(w_even, wv, h, m);                    // rows e - 1 and e share their XOR term
-                                    *reinterpret_cast<uint16_t*>(bp - BF_ROWB) = (uint16_t)h;
-                                    *reinterpret_cast<uint16_t*>(bp - BF_ROWB + BF_TERM) = (uint16_t)m;
-                                    *reinterpret_cast<uint16_t*>(bp) = (uint16_t)(h >> 16);
-                                    *reinterpret_cast<uint16_t*>(bp + BF_TERM) = (uint16_t)(m >> 16);
-                                }
-                            } else {
                             float* const wp = reinterpret_cast<float*>(my_wt + (wofs_b ^ (uint32_t)(16 * (NE * p + k))));
                             wp[0] = wv;
                             if constexpr (GEO) {
                                 const float dL_dalpha = fmaf(Tb, qd[k], -(S * f[k]));
                                 S = fmaf(wv, qd[k], S);
                                 wp[ST_OFS] = au[k] * dL_dalpha;
-                            }
                             }
                             T = Tb;
                         }
@@ -697,13 +674,15 @@ __device__ __forceinline__ void render_backward_pl_body(const BwdArgs& a) {
                 if (active && (tt & 0xFFFFu) != 0) {
                     const int lane2 = fresh_lane();
                     const int col = lane2 & 15, kk = lane2 >> 4;
-                    // operand read base of lane (row col, K group kk): unit 4 ks + kk at slot (4 ks + kk) ^ (row >> 1)
-                    const uint32_t r0 = (uint32_t)(col * BF_ROWB + ((kk ^ (col >> 1)) & 7) * 16), r1 = r0 ^ 64u;
+                    // transposed-read addresses of this lane (pl_phase1.h, bf_tr_ofs): the two halves of an A fragment of span 0
+                    const uint32_t r0 = bf_tr_ofs((uint32_t)lane2, 0), r1 = r0 ^ 0x88u;
                     const int fs_row0 = (4 * kk) * FS;
                     const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
+                    // (EXEC is all ones here: every condition around the reads is wave-uniform, as ds_read_b64_tr_b16 requires)
                     auto a_read = [&](int qd, int term, int ks, uint32_t (&dst)[4]) {
-                        const uint4 v = *reinterpret_cast<const uint4*>(bf_tiles + qd * BF_QUAD + term * BF_TERM + (ks ? r1 : r0));
-                        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+                        const char* const img = bf_tiles + qd * BF_QUAD + term * BF_TERM + ks * BF_SPAN;
+                        const u32x2 v0 = lds_read_tr16(img + r0), v1 = lds_read_tr16(img + r1);
+                        dst[0] = v0.x; dst[1] = v0.y; dst[2] = v1.x; dst[3] = v1.y;
                     };
                     if (use_s) {
                         // the moment wave: s = s_hi + s_mid against the exact monomials, the four quadrants kept apart

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     P1Pixel px;
     px.pxf = (float)(lane & 7) + seed; px.pyf = (float)(lane >> 3); px.last = 1000000u - (uint32_t)lane;
     px.dR = 1e-6f * (float)(lane + 1); px.dG = -2e-6f; px.dB = 3e-6f; px.dD = seed * 1e-7f;
-    const uint32_t sofs = (uint32_t)(q * BF_QUAD + (lane >> 3) * 16 + (lane & 7) * 2);
+    const uint32_t sofs = bf_store_base((uint32_t)q, (uint32_t)lane);
     float T = 0.f, S = 0.f;
     uint32_t tm = 0;
     const unsigned long long t0 = __builtin_readcyclecounter();
