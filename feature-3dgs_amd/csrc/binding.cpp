@@ -18,6 +18,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/extension.h>
 
+#include <array>
 #include <exception>
 #include <stdexcept>
 #include <string>
@@ -386,6 +387,63 @@ torch::Tensor FeatureDecode(const torch::Tensor& feature_map, int64_t Hg, int64_
     return out;
 }
 
+// fused L1 + D-SSIM image loss (include/f3dgs.h: f3dgs_image_loss_forward); image and gt (C,H,W) or (N,C,H,W).  Returns
+// (loss, l1, ssim, per-image ssim (N) or empty, scratch); with want_grad the scratch holds what image_loss_backward reads.
+static void image_loss_check(const torch::Tensor& image, const torch::Tensor& gt) {
+    TORCH_CHECK(image.is_cuda() && gt.is_cuda(), "image_loss: image and gt must live on a HIP device (no CPU path)");
+    TORCH_CHECK(image.device() == gt.device(), "image_loss: image and gt are on different devices");
+    TORCH_CHECK(image.scalar_type() == torch::kFloat32 && gt.scalar_type() == torch::kFloat32,
+                "image_loss: image and gt must be float32 (got ", image.scalar_type(), ", ", gt.scalar_type(), ")");
+    TORCH_CHECK(image.dim() == 3 || image.dim() == 4, "image_loss: a (C,H,W) or (N,C,H,W) image expected, got ", image.dim(), " dimensions");
+    TORCH_CHECK(image.sizes() == gt.sizes(), "image_loss: image ", image.sizes(), " and gt ", gt.sizes(), " shapes differ");
+    TORCH_CHECK(image.numel() > 0, "image_loss: empty image");
+}
+
+static std::array<int, 4> image_loss_dims(const torch::Tensor& t) {
+    if (t.dim() == 3) return {1, (int)t.size(0), (int)t.size(1), (int)t.size(2)};
+    return {(int)t.size(0), (int)t.size(1), (int)t.size(2), (int)t.size(3)};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+ImageLossForward(const torch::Tensor& image, const torch::Tensor& gt, double lambda_dssim, bool want_grad, bool per_image) {
+    image_loss_check(image, gt);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(image.device());
+    auto im = dev_f32(image, "image"), g = dev_f32(gt, "gt");
+    const auto d = image_loss_dims(im);
+    auto o = im.options();
+    torch::Tensor loss = torch::empty({}, o), l1 = torch::empty({}, o), ssim = torch::empty({}, o);
+    torch::Tensor ssim_img = per_image ? torch::empty({d[0]}, o) : torch::empty({0}, o);
+    torch::Tensor scratch = torch::empty({(long long)f3dgs_image_loss_scratch_bytes(d[0], d[1], d[2], d[3], want_grad ? 1 : 0)},
+                                         o.dtype(torch::kByte));
+    const int rc = f3dgs_image_loss_forward(d[0], d[1], d[2], d[3], im.data_ptr<float>(), g.data_ptr<float>(), (float)lambda_dssim,
+                                            want_grad ? 1 : 0, loss.data_ptr<float>(), l1.data_ptr<float>(), ssim.data_ptr<float>(),
+                                            per_image ? ssim_img.data_ptr<float>() : nullptr, scratch.data_ptr(), current_stream(im));
+    check_status(rc, "image_loss_forward");
+    return std::make_tuple(loss, l1, ssim, ssim_img, scratch);
+}
+
+// the gradient with respect to `image` (include/f3dgs.h: f3dgs_image_loss_backward); `upstream` one value (modes 0, 1) or N
+// (mode 2), on the device
+torch::Tensor ImageLossBackward(const torch::Tensor& image, const torch::Tensor& gt, const torch::Tensor& scratch,
+                                const torch::Tensor& upstream, double lambda_dssim, int64_t mode) {
+    image_loss_check(image, gt);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(image.device());
+    auto im = dev_f32(image, "image"), g = dev_f32(gt, "gt");
+    const auto d = image_loss_dims(im);
+    TORCH_CHECK(scratch.is_cuda() && scratch.is_contiguous() &&
+                    scratch.numel() == (int64_t)f3dgs_image_loss_scratch_bytes(d[0], d[1], d[2], d[3], 1),
+                "image_loss_backward: scratch is not what a want_grad forward call on this shape returned");
+    auto u = dev_f32(upstream, "upstream");
+    TORCH_CHECK(u.numel() == (mode == F3DGS_IMAGE_LOSS_SSIM_PER_IMAGE ? d[0] : 1), "image_loss_backward: upstream gradient of ",
+                u.numel(), " values for mode ", mode);
+    torch::Tensor d_image = torch::empty_like(im);
+    const int rc = f3dgs_image_loss_backward(d[0], d[1], d[2], d[3], im.data_ptr<float>(), g.data_ptr<float>(), (float)lambda_dssim,
+                                             (int)mode, u.data_ptr<float>(), scratch.data_ptr(), d_image.data_ptr<float>(),
+                                             current_stream(im));
+    check_status(rc, "image_loss_backward");
+    return d_image;
+}
+
 void AdamStep(torch::Tensor& param, const torch::Tensor& grad, torch::Tensor& exp_avg, torch::Tensor& exp_avg_sq, double lr,
               double beta1, double beta2, double eps, int64_t step, const c10::optional<torch::Tensor>& row_mask) {
     TORCH_CHECK(param.is_cuda() && grad.is_cuda() && exp_avg.is_cuda() && exp_avg_sq.is_cuda(), "adam_step: HIP tensors only");
@@ -499,6 +557,13 @@ PYBIND11_MODULE(_C, m) {
           "gx (Hg, Wg, C) float32 = dL/d(resized feature map) as feature_l1 returns it, scale = 0-dim device tensor or None: the NEXT "
           "rasterize_gaussians_backward call takes its feature-map gradient from there (transposed resize applied per tile); None clears");
     m.def("feature_decode", &FeatureDecode);
+    m.def("image_loss_forward", &ImageLossForward, py::arg("image"), py::arg("gt"), py::arg("lambda_dssim"), py::arg("want_grad"),
+          py::arg("per_image") = false);
+    m.def("image_loss_backward", &ImageLossBackward, py::arg("image"), py::arg("gt"), py::arg("scratch"), py::arg("upstream"),
+          py::arg("lambda_dssim"), py::arg("mode"));
+    m.attr("IMAGE_LOSS_L1_DSSIM") = (int)F3DGS_IMAGE_LOSS_L1_DSSIM;
+    m.attr("IMAGE_LOSS_SSIM") = (int)F3DGS_IMAGE_LOSS_SSIM;
+    m.attr("IMAGE_LOSS_SSIM_PER_IMAGE") = (int)F3DGS_IMAGE_LOSS_SSIM_PER_IMAGE;
     m.def("adam_step", &AdamStep, py::arg("param"), py::arg("grad"), py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("lr"),
           py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("step"), py::arg("row_mask") = py::none());
     m.def("adam_step_multi", &AdamStepMulti, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("lrs"),

@@ -285,6 +285,9 @@ size_t feature_decode_scratch_bytes(int C, int Hg, int Wg, bool decoder);
 hipError_t launch_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
                                  const float* bias, void* out, bool half, char* scratch, hipStream_t s);
 
+// api.hip: sets the text f3dgs_last_error() returns (for the entry points defined in other files); returns `code`
+int report_error(int code, const char* msg);
+
 // adam.hip
 void launch_adam_step(size_t n, float* p, const float* g, float* m, float* v, double lr, double b1, double b2, double eps,
                       int step, const uint8_t* row_mask, size_t width, hipStream_t s);

@@ -63,7 +63,7 @@ extern "C" {
  * resizeFunctional() of rasterize_points.cu:27-33. */
 typedef char* (*f3dgs_resize_fn)(void* ctx, size_t nbytes);
 
-/* Library / ABI version: major*10000 + minor*100 + patch (3.5.0 -> 30500). */
+/* Library / ABI version: major*10000 + minor*100 + patch (3.6.0 -> 30600). */
 int f3dgs_version(void);
 
 /* Thread-local message of the last error raised on this host thread. */
@@ -327,6 +327,33 @@ const float* f3dgs_feature_l1_lowres_grad(int C, int Cout, int Hg, int Wg, int h
  * an argument error) -; gx == NULL clears it.  The kernel reads exactly the Hg*Wg*C floats of `gx`, nothing beyond them.
  */
 int f3dgs_set_feature_grad_lowres(const float* gx, int Hg, int Wg, const float* scale);
+
+/*
+ * Fused image loss (the other half of train.py:99-105): (1 - lambda) * l1_loss(image, gt) + lambda * (1 - ssim(image, gt))
+ * of utils/loss_utils.py:17-18, :33-63 at window_size 11 (Gaussian window, sigma 1.5, zero padding 5, C1 = 0.01^2,
+ * C2 = 0.03^2), forward and backward.  image, gt: N x C x H x W fp32, contiguous (a C x H x W image is N = 1); any
+ * N, C, H, W >= 1, images smaller than the window included.  All outputs are device pointers; nothing is read back to the
+ * host, no memset is issued and every launch goes to `stream`: both calls may be captured into a graph.  The loss is
+ * deterministic (partial sums reduced in a fixed order).
+ *
+ * f3dgs_image_loss_forward writes *loss, *l1 = mean |image - gt|, *ssim = mean SSIM over all N*C*H*W elements and, if
+ * ssim_per_image is not NULL, the N per-image means (size_average=False).  want_grad != 0: it also leaves in `scratch`
+ * (f3dgs_image_loss_scratch_bytes(N, C, H, W, want_grad) bytes) the three per-pixel fp32 maps the backward call reads.
+ *
+ * f3dgs_image_loss_backward writes d_image (N x C x H x W), the gradient with respect to `image` (none is formed for gt) of
+ *   mode F3DGS_IMAGE_LOSS_L1_DSSIM        the loss above;                          upstream: one device scalar
+ *   mode F3DGS_IMAGE_LOSS_SSIM            the mean SSIM;                           upstream: one device scalar
+ *   mode F3DGS_IMAGE_LOSS_SSIM_PER_IMAGE  the N per-image means (a vector output); upstream: N device values
+ * times the upstream gradient.  `scratch` is the buffer a want_grad forward call on the same image and gt filled.
+ */
+#define F3DGS_IMAGE_LOSS_L1_DSSIM 0
+#define F3DGS_IMAGE_LOSS_SSIM 1
+#define F3DGS_IMAGE_LOSS_SSIM_PER_IMAGE 2
+size_t f3dgs_image_loss_scratch_bytes(int N, int C, int H, int W, int want_grad);
+int f3dgs_image_loss_forward(int N, int C, int H, int W, const float* image, const float* gt, float lambda_dssim, int want_grad,
+                             float* loss, float* l1, float* ssim, float* ssim_per_image, void* scratch, void* stream);
+int f3dgs_image_loss_backward(int N, int C, int H, int W, const float* image, const float* gt, float lambda_dssim, int mode,
+                              const float* upstream, const void* scratch, float* d_image, void* stream);
 
 /*
  * Forward-only counterpart (the inference side, render.py:169-171, :137-139, :294-296): the rendered feature map (C,H,W)
