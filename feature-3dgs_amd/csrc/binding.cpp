@@ -444,6 +444,50 @@ torch::Tensor ImageLossBackward(const torch::Tensor& image, const torch::Tensor&
     return d_image;
 }
 
+// language-guided selection (include/f3dgs.h: f3dgs_edit_select).  features (P, C) float32, contiguous and 16-byte aligned where
+// normalize_inplace asks for the write-back (edit.py copies other views and copies back); text (K, C).  Returns (mask (P),
+// score (P) or None, opacity_out like opacity or None).
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+EditSelect(torch::Tensor& features, const torch::Tensor& text, uint64_t positive_mask, int64_t first_positive, int64_t variant,
+           const c10::optional<double>& threshold, bool normalize_inplace, bool want_score,
+           const c10::optional<torch::Tensor>& opacity) {
+    TORCH_CHECK(features.is_cuda() && text.is_cuda(), "edit_select: features and text must live on a HIP device (no CPU path)");
+    TORCH_CHECK(features.device() == text.device(), "edit_select: features and text are on different devices");
+    TORCH_CHECK(features.scalar_type() == torch::kFloat32 && text.scalar_type() == torch::kFloat32,
+                "edit_select: features and text must be float32 (got ", features.scalar_type(), ", ", text.scalar_type(), ")");
+    TORCH_CHECK(features.dim() == 2 && text.dim() == 2 && features.size(1) == text.size(1) && text.size(0) >= 1 && text.size(1) >= 1,
+                "edit_select: features (P, C) and text (K, C) expected, got ", features.sizes(), " and ", text.sizes());
+    TORCH_CHECK(features.size(0) <= (1 << 30), "edit_select: too many rows");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(features.device());
+    torch::Tensor f = features;
+    if (normalize_inplace) {
+        TORCH_CHECK(features.is_contiguous(), "edit_select: normalize_inplace needs contiguous features");
+    } else {
+        f = features.contiguous();
+    }
+    const torch::Tensor t = text.contiguous();
+    const int P = (int)f.size(0), C = (int)f.size(1), K = (int)t.size(0);
+    auto o = f.options();
+    torch::Tensor mask = torch::empty({P}, o);
+    c10::optional<torch::Tensor> score, op_out;
+    if (want_score) score = torch::empty({P}, o);
+    torch::Tensor op_in;
+    if (opacity.has_value()) {
+        TORCH_CHECK(opacity->is_cuda() && opacity->scalar_type() == torch::kFloat32 && opacity->numel() == P,
+                    "edit_select: opacity must be ", P, " float32 values on the device");
+        op_in = opacity->contiguous();
+        op_out = torch::empty_like(op_in);
+    }
+    const int rc = f3dgs_edit_select(P, C, K, fptr(f), normalize_inplace ? f.data_ptr<float>() : nullptr, t.data_ptr<float>(),
+                                     positive_mask, (int)first_positive, (int)variant, threshold.has_value() ? 1 : 0,
+                                     threshold.has_value() ? (float)*threshold : 0.f, P ? mask.data_ptr<float>() : nullptr,
+                                     (want_score && P) ? score->data_ptr<float>() : nullptr,
+                                     (op_out.has_value() && P) ? op_in.data_ptr<float>() : nullptr,
+                                     (op_out.has_value() && P) ? op_out->data_ptr<float>() : nullptr, current_stream(f));
+    check_status(rc, "edit_select");
+    return std::make_tuple(mask, score, op_out);
+}
+
 void AdamStep(torch::Tensor& param, const torch::Tensor& grad, torch::Tensor& exp_avg, torch::Tensor& exp_avg_sq, double lr,
               double beta1, double beta2, double eps, int64_t step, const c10::optional<torch::Tensor>& row_mask) {
     TORCH_CHECK(param.is_cuda() && grad.is_cuda() && exp_avg.is_cuda() && exp_avg_sq.is_cuda(), "adam_step: HIP tensors only");
@@ -564,6 +608,15 @@ PYBIND11_MODULE(_C, m) {
     m.attr("IMAGE_LOSS_L1_DSSIM") = (int)F3DGS_IMAGE_LOSS_L1_DSSIM;
     m.attr("IMAGE_LOSS_SSIM") = (int)F3DGS_IMAGE_LOSS_SSIM;
     m.attr("IMAGE_LOSS_SSIM_PER_IMAGE") = (int)F3DGS_IMAGE_LOSS_SSIM_PER_IMAGE;
+    m.def("edit_select", &EditSelect, py::arg("features"), py::arg("text"), py::arg("positive_mask"), py::arg("first_positive"),
+          py::arg("variant"), py::arg("threshold") = py::none(), py::arg("normalize_inplace") = false, py::arg("want_score") = false,
+          py::arg("opacity") = py::none());
+    m.attr("EDIT_SELECT") = (int)F3DGS_EDIT_SELECT;
+    m.attr("EDIT_DELETE") = (int)F3DGS_EDIT_DELETE;
+    m.attr("EDIT_TEXT_NORMALIZED") = (int)F3DGS_EDIT_TEXT_NORMALIZED;
+    m.attr("EDIT_FILL_UNSELECTED") = (int)F3DGS_EDIT_FILL_UNSELECTED;
+    m.attr("EDIT_MAX_TEXTS") = (int)F3DGS_EDIT_MAX_TEXTS;
+    m.attr("EDIT_MAX_TEXT_ELEMENTS") = (int)F3DGS_EDIT_MAX_TEXT_ELEMENTS;
     m.def("adam_step", &AdamStep, py::arg("param"), py::arg("grad"), py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("lr"),
           py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("step"), py::arg("row_mask") = py::none());
     m.def("adam_step_multi", &AdamStepMulti, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("lrs"),

@@ -63,7 +63,7 @@ extern "C" {
  * resizeFunctional() of rasterize_points.cu:27-33. */
 typedef char* (*f3dgs_resize_fn)(void* ctx, size_t nbytes);
 
-/* Library / ABI version: major*10000 + minor*100 + patch (3.6.0 -> 30600). */
+/* Library / ABI version: major*10000 + minor*100 + patch (3.7.0 -> 30700). */
 int f3dgs_version(void);
 
 /* Thread-local message of the last error raised on this host thread. */
@@ -354,6 +354,45 @@ int f3dgs_image_loss_forward(int N, int C, int H, int W, const float* image, con
                              float* loss, float* l1, float* ssim, float* ssim_per_image, void* scratch, void* stream);
 int f3dgs_image_loss_backward(int N, int C, int H, int W, const float* image, const float* gt, float lambda_dssim, int mode,
                               const float* upstream, const void* scratch, float* d_image, void* stream);
+
+/*
+ * Language-guided editing (gaussian_renderer/__init__.py:21-55, calculate_selection_score and
+ * calculate_selection_score_delete; render_edit :131-148 calls them for every edited frame): which rows of the (P, C) fp32
+ * feature table match the K text embeddings `text` (K x C fp32), in one pass over the table.  Per row f, in the reference's
+ * number formats: n = ||f||_2 and f^ = f / n in fp32 (written to normalized_out if that is not NULL; it may alias
+ * `features`, the reference's in-place `features /= ...`); f^ and the fp32-normalised text rows rounded to fp16;
+ * s_k = f^ . t^_k rounded to fp16; for K > 1 the softmax p over the K scores, every p_k rounded to fp16 (both carried in
+ * fp64 and rounded once: the fp16 neighbour of the exact value, which the reference's fp32 evaluations scatter around).  Then, on those fp16 values (pos = the columns of positive_mask, first = first_positive, i.e.
+ * positive_ids[0]; q = fp16(sum of p_k over pos); v = p with column `first` replaced by q; m = (argmax_k v_k is in pos),
+ * NaN counting as the maximum and the lowest column winning a tie; q2 = fp16(sum of v_k over pos), which counts the
+ * positives other than `first` twice, as the reference does):
+ *
+ *   K = 1 (a threshold is required)      mask = s_0 >= threshold                  score_out = s_0
+ *   select, K > 1, has_threshold         mask = q >= threshold                    score_out = q
+ *   select, K > 1, no threshold          mask = m                                 score_out = q
+ *   delete, K > 1, has_threshold         mask = m or q2 >= threshold              score_out = q2
+ *   delete, K > 1, no threshold          mask = m                                 score_out = q
+ *
+ * A row of zero norm or with a non-finite element has NaN scores: every >= is false and the argmax is column 0.
+ * mask_out: P floats, 0 or 1.  score_out: NULL or P floats.  opacity_in / opacity_out (both NULL or both given, P floats,
+ * may alias): render_edit's masked fill fused, opacity_out = 0 where the mask is set (F3DGS_EDIT_FILL_UNSELECTED: where
+ * it is NOT set, the extraction), opacity_in elsewhere.  `variant` is F3DGS_EDIT_SELECT or F3DGS_EDIT_DELETE, optionally
+ * or-ed with F3DGS_EDIT_TEXT_NORMALIZED (the rows of `text` are already t / ||t|| in fp32: the kernel only rounds them)
+ * and F3DGS_EDIT_FILL_UNSELECTED.  Limits: K <= F3DGS_EDIT_MAX_TEXTS and K * C <= F3DGS_EDIT_MAX_TEXT_ELEMENTS (the fp16
+ * text block lives in 64 KB of LDS); positive_mask non-empty with no bit at or above K and bit first_positive set.
+ * Rows are read with 16-byte loads when C % 4 == 0, C <= 2048 and the pointers are 16-byte aligned; anything else takes a
+ * slower scalar path.  No scratch, no host read, no memset; one launch on `stream`: capturable.  P = 0 is a no-op.
+ */
+#define F3DGS_EDIT_SELECT 0
+#define F3DGS_EDIT_DELETE 1
+#define F3DGS_EDIT_TEXT_NORMALIZED 0x100
+#define F3DGS_EDIT_FILL_UNSELECTED 0x200
+#define F3DGS_EDIT_MAX_TEXTS 64
+#define F3DGS_EDIT_MAX_TEXT_ELEMENTS 32768
+int f3dgs_edit_select(int P, int C, int K, const float* features, float* normalized_out, const float* text,
+                      uint64_t positive_mask, int first_positive, int variant, int has_threshold, float threshold,
+                      float* mask_out, float* score_out, const float* opacity_in, float* opacity_out,
+                      void* stream /* hipStream_t */);
 
 /*
  * Forward-only counterpart (the inference side, render.py:169-171, :137-139, :294-296): the rendered feature map (C,H,W)
