@@ -377,7 +377,7 @@ CountReadback* count_readback(hipStream_t s, bool may_create) {
 
 extern "C" {
 
-int f3dgs_version(void) { return 30700; }   // 3.7.0 (major * 10000 + minor * 100 + patch): 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
+int f3dgs_version(void) { return 30800; }   // 3.8.0 (major * 10000 + minor * 100 + patch): 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
 
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 
@@ -834,6 +834,33 @@ int f3dgs_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const fl
     }
     HIP_TRY(launch_feature_decode(C, H, W, Cout, Hg, Wg, feature_map, weight, bias, out, out_is_half != 0,
                                   static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+size_t f3dgs_segment_scratch_bytes(int C, int Cout, int Hs, int Ws, int K, int has_decoder) {
+    if (C <= 0 || Cout <= 0 || Hs < 0 || Ws < 0 || K <= 0 || (long long)Hs * Ws > (1ll << 30)) return 0;
+    return segment_scratch_bytes(C, Cout, Hs, Ws, K, has_decoder != 0);
+}
+
+int f3dgs_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const float* feature_map, const float* weight,
+                  const float* bias, const float* text, int flags, int64_t* labels, float* score, void* scratch, void* stream) {
+    if (C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Hs < 0 || Ws < 0 || K <= 0)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: bad sizes C=%d H=%d W=%d Cout=%d Hs=%d Ws=%d K=%d", C, H, W, Cout, Hs, Ws, K);
+    const int known = F3DGS_SEGMENT_ROUND_HALF | F3DGS_SEGMENT_TEXT_NORMALIZED;
+    if (flags & ~known) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: unknown flag bits 0x%x", flags & ~known);
+    if ((weight == nullptr) != (bias == nullptr)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: weight and bias go together");
+    if (!weight && Cout != C)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: without a decoder the text has C = %d channels, got %d", C, Cout);
+    if (K > F3DGS_SEGMENT_MAX_TEXTS) return fail(F3DGS_ERR_UNSUPPORTED, "segment: K=%d beyond the limit of %d text rows", K, F3DGS_SEGMENT_MAX_TEXTS);
+    if (weight && (!feature_l1_decoder_supported(C) || Cout % 32 != 0))
+        return fail(F3DGS_ERR_UNSUPPORTED, "segment: decoder %d -> %d: supported are input widths 32, 64, 128 and outputs that are multiples of 32", C, Cout);
+    if ((long long)Hs * Ws > (1ll << 30) || (long long)H * W > (1ll << 28)) return fail(F3DGS_ERR_UNSUPPORTED, "segment: too large");
+    if (Hs == 0 || Ws == 0) return F3DGS_OK;
+    const bool text_normalized = (flags & F3DGS_SEGMENT_TEXT_NORMALIZED) != 0;
+    if (!feature_map || !text || !labels) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: null pointer");
+    if (!scratch && (weight || !text_normalized)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: scratch is null");
+    HIP_TRY(launch_segment(C, H, W, Cout, Hs, Ws, K, feature_map, weight, bias, text, (flags & F3DGS_SEGMENT_ROUND_HALF) != 0,
+                           text_normalized, labels, score, static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
     return F3DGS_OK;
 }
 

@@ -488,6 +488,44 @@ EditSelect(torch::Tensor& features, const torch::Tensor& text, uint64_t positive
     return std::make_tuple(mask, score, op_out);
 }
 
+// open-vocabulary segmentation (include/f3dgs.h: f3dgs_segment).  feature_map (C,H,W), text (K,Cout) float32; weight (Cout,C) /
+// bias (Cout) or empty tensors.  Returns (labels (Hs,Ws) int64, score (Hs,Ws) float32 or None).
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>>
+Segment(const torch::Tensor& feature_map, const torch::Tensor& text, int64_t Hs, int64_t Ws, const torch::Tensor& weight,
+        const torch::Tensor& bias, int64_t flags, bool want_score) {
+    TORCH_CHECK(feature_map.is_cuda() && text.is_cuda(), "segment: feature_map and text must live on a HIP device (no CPU path)");
+    TORCH_CHECK(feature_map.device() == text.device(), "segment: feature_map and text are on different devices");
+    TORCH_CHECK(feature_map.scalar_type() == torch::kFloat32 && text.scalar_type() == torch::kFloat32,
+                "segment: feature_map and text must be float32 (got ", feature_map.scalar_type(), ", ", text.scalar_type(), ")");
+    TORCH_CHECK(feature_map.dim() == 3 && text.dim() == 2, "segment: feature_map (C,H,W) and text (K,Cout) expected");
+    TORCH_CHECK(Hs >= 0 && Ws >= 0 && Hs * Ws <= (1ll << 30), "segment: bad output size");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(feature_map.device());
+    auto fm = feature_map.contiguous(), t = text.contiguous();
+    const bool dec = weight.numel() > 0;
+    torch::Tensor w = weight, b = bias;
+    const int C = fm.size(0), H = fm.size(1), W = fm.size(2), K = t.size(0);
+    int Cout = C;
+    if (dec) {
+        w = dev_f32(weight, "weight");
+        b = dev_f32(bias, "bias");
+        TORCH_CHECK(w.dim() == 2 && w.size(1) == C && b.numel() == w.size(0), "segment: weight (Cout,C) / bias (Cout) do not match feature_map");
+        Cout = w.size(0);
+    }
+    TORCH_CHECK(t.size(1) == Cout, "segment: text has ", t.size(1), " channels, the scored map ", Cout);
+    torch::Tensor labels = torch::empty({Hs, Ws}, fm.options().dtype(torch::kInt64));
+    c10::optional<torch::Tensor> score;
+    if (want_score) score = torch::empty({Hs, Ws}, fm.options());
+    torch::Tensor scratch = torch::empty({(long long)f3dgs_segment_scratch_bytes(C, Cout, (int)Hs, (int)Ws, K, dec ? 1 : 0)},
+                                         fm.options().dtype(torch::kByte));
+    const bool any = Hs * Ws > 0;
+    const int rc = f3dgs_segment(C, H, W, Cout, (int)Hs, (int)Ws, K, fm.data_ptr<float>(), dec ? w.data_ptr<float>() : nullptr,
+                                 dec ? b.data_ptr<float>() : nullptr, t.data_ptr<float>(), (int)flags,
+                                 any ? labels.data_ptr<int64_t>() : nullptr, (want_score && any) ? score->data_ptr<float>() : nullptr,
+                                 scratch.data_ptr(), current_stream(fm));
+    check_status(rc, "segment");
+    return std::make_tuple(labels, score);
+}
+
 void AdamStep(torch::Tensor& param, const torch::Tensor& grad, torch::Tensor& exp_avg, torch::Tensor& exp_avg_sq, double lr,
               double beta1, double beta2, double eps, int64_t step, const c10::optional<torch::Tensor>& row_mask) {
     TORCH_CHECK(param.is_cuda() && grad.is_cuda() && exp_avg.is_cuda() && exp_avg_sq.is_cuda(), "adam_step: HIP tensors only");
@@ -611,6 +649,11 @@ PYBIND11_MODULE(_C, m) {
     m.def("edit_select", &EditSelect, py::arg("features"), py::arg("text"), py::arg("positive_mask"), py::arg("first_positive"),
           py::arg("variant"), py::arg("threshold") = py::none(), py::arg("normalize_inplace") = false, py::arg("want_score") = false,
           py::arg("opacity") = py::none());
+    m.def("segment", &Segment, py::arg("feature_map"), py::arg("text"), py::arg("Hs"), py::arg("Ws"), py::arg("weight"), py::arg("bias"),
+          py::arg("flags"), py::arg("want_score"));
+    m.attr("SEGMENT_ROUND_HALF") = (int)F3DGS_SEGMENT_ROUND_HALF;
+    m.attr("SEGMENT_TEXT_NORMALIZED") = (int)F3DGS_SEGMENT_TEXT_NORMALIZED;
+    m.attr("SEGMENT_MAX_TEXTS") = (int)F3DGS_SEGMENT_MAX_TEXTS;
     m.attr("EDIT_SELECT") = (int)F3DGS_EDIT_SELECT;
     m.attr("EDIT_DELETE") = (int)F3DGS_EDIT_DELETE;
     m.attr("EDIT_TEXT_NORMALIZED") = (int)F3DGS_EDIT_TEXT_NORMALIZED;

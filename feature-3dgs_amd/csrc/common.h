@@ -284,6 +284,14 @@ hipError_t launch_feature_l1(int C, int H, int W, int Cout, int Hg, int Wg, cons
 size_t feature_decode_scratch_bytes(int C, int Hg, int Wg, bool decoder);
 hipError_t launch_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
                                  const float* bias, void* out, bool half, char* scratch, hipStream_t s);
+// the decode's resize stage alone: (C,H,W) -> pixel-major X[Hg Wg][C] (segment.hip feeds its own decoder loop from it)
+void launch_feature_resize(int C, int H, int W, int Hg, int Wg, const float* feature_map, float* X, hipStream_t s);
+
+// segment.hip
+size_t segment_scratch_bytes(int C, int Cout, int Hs, int Ws, int K, bool decoder);
+hipError_t launch_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const float* feature_map, const float* weight,
+                          const float* bias, const float* text, bool round_half, bool text_normalized, int64_t* labels,
+                          float* score, char* scratch, hipStream_t s);
 
 // api.hip: sets the text f3dgs_last_error() returns (for the entry points defined in other files); returns `code`
 int report_error(int code, const char* msg);

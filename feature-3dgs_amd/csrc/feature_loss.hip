@@ -635,6 +635,12 @@ hipError_t launch_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, 
     return hipErrorInvalidValue;
 }
 
+void launch_feature_resize(int C, int H, int W, int Hg, int Wg, const float* feature_map, float* X, hipStream_t s) {
+    const int N = Hg * Wg;
+    hipLaunchKernelGGL(fl_resize_kernel, dim3((N + 63) / 64, (C + 31) / 32), dim3(256), 0, s, make_resize_geom(H, W, Hg, Wg), C,
+                       feature_map, X, nullptr, 0.f, nullptr);
+}
+
 hipError_t launch_feature_l1(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
                              const float* bias, const float* gt, float* loss, float* d_feature_map, float* d_weight,
                              float* d_bias, char* scratch, hipStream_t s) {

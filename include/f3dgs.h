@@ -63,7 +63,7 @@ extern "C" {
  * resizeFunctional() of rasterize_points.cu:27-33. */
 typedef char* (*f3dgs_resize_fn)(void* ctx, size_t nbytes);
 
-/* Library / ABI version: major*10000 + minor*100 + patch (3.7.0 -> 30700). */
+/* Library / ABI version: major*10000 + minor*100 + patch (3.8.0 -> 30800). */
 int f3dgs_version(void);
 
 /* Thread-local message of the last error raised on this host thread. */
@@ -403,6 +403,30 @@ int f3dgs_edit_select(int P, int C, int K, const float* features, float* normali
 size_t f3dgs_feature_decode_scratch_bytes(int C, int Hg, int Wg, int has_decoder);
 int f3dgs_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
                          const float* bias, void* out, int out_is_half, void* scratch, void* stream);
+
+/*
+ * Open-vocabulary segmentation of a rendered view (render.py:168-180 followed by encoders/lseg_encoder/segmentation.py:526-540):
+ * the rendered feature map (C,H,W) is resized (bilinear, align_corners=True) to (Hs,Ws), decoded by the 1x1 conv if weight /
+ * bias are given (the values of f3dgs_feature_decode, bit for bit), with F3DGS_SEGMENT_ROUND_HALF rounded to IEEE fp16 and back
+ * (render.py stores the map as fp16, and that rounding decides labels), and every pixel's Cout-vector D is scored against the
+ * K rows of `text` (K x Cout fp32): score_k = (D . t_k / ||t_k||) / ||D||, labels = argmax_k score_k (int64, Hs*Ws), `score`
+ * (NULL or Hs*Ws floats) the winning score.  All arithmetic is fp32.  NaN counts as the maximum and the lowest index wins a
+ * tie (torch.max): a pixel of zero norm or with a non-finite value gets label 0 and score NaN.  Neither the decoded
+ * (Cout,Hs,Ws) map nor the (Hs*Ws,K) logits are ever written to memory.  F3DGS_SEGMENT_TEXT_NORMALIZED: the rows of `text`
+ * are already t / ||t|| and are used as they are.  `text` is never modified.
+ * With a decoder C must be 32, 64 or 128 and Cout a multiple of 32; without one (weight == bias == NULL) Cout must equal C,
+ * any C >= 1, and (Hs,Ws) == (H,W) is no resize at all: every pixel is scored as it is (an already decoded map).
+ * 1 <= K <= F3DGS_SEGMENT_MAX_TEXTS.  Other shapes: F3DGS_ERR_UNSUPPORTED.  `scratch`:
+ * f3dgs_segment_scratch_bytes(...) bytes (the resized map with a decoder, and the normalised text).  No host read, no memset,
+ * no allocation; every launch goes to `stream`: capturable.  Hs * Ws == 0 is a no-op.
+ */
+#define F3DGS_SEGMENT_ROUND_HALF 0x1
+#define F3DGS_SEGMENT_TEXT_NORMALIZED 0x2
+#define F3DGS_SEGMENT_MAX_TEXTS 256
+size_t f3dgs_segment_scratch_bytes(int C, int Cout, int Hs, int Ws, int K, int has_decoder);
+int f3dgs_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const float* feature_map, const float* weight,
+                  const float* bias, const float* text /* K x Cout */, int flags, int64_t* labels /* Hs*Ws */,
+                  float* score /* Hs*Ws or NULL */, void* scratch, void* stream /* hipStream_t */);
 
 /*
  * One torch.optim.Adam step (no weight decay, no amsgrad: the reference's configuration,
