@@ -526,6 +526,13 @@ Segment(const torch::Tensor& feature_map, const torch::Tensor& text, int64_t Hs,
     return std::make_tuple(labels, score);
 }
 
+// One byte per row, non-zero where the mask is: bool / uint8 masks as they are, wider types through `!= 0` (a cast to
+// uint8 would wrap: an int32 `radii` of 256 handed in as the mask would read as "not visible").
+static torch::Tensor mask_bytes(const torch::Tensor& row_mask) {
+    if (row_mask.scalar_type() == torch::kBool || row_mask.scalar_type() == torch::kUInt8) return row_mask.contiguous();
+    return row_mask.ne(0);
+}
+
 void AdamStep(torch::Tensor& param, const torch::Tensor& grad, torch::Tensor& exp_avg, torch::Tensor& exp_avg_sq, double lr,
               double beta1, double beta2, double eps, int64_t step, const c10::optional<torch::Tensor>& row_mask) {
     TORCH_CHECK(param.is_cuda() && grad.is_cuda() && exp_avg.is_cuda() && exp_avg_sq.is_cuda(), "adam_step: HIP tensors only");
@@ -541,8 +548,8 @@ void AdamStep(torch::Tensor& param, const torch::Tensor& grad, torch::Tensor& ex
     if (row_mask.has_value() && row_mask->defined()) {
         TORCH_CHECK(param.dim() >= 1 && row_mask->numel() == param.size(0), "adam_step: one mask entry per row");
         TORCH_CHECK(row_mask->is_cuda(), "adam_step: the mask must be a HIP tensor");
-        mk = row_mask->to(torch::kUInt8).contiguous();      // bool / uint8 / int masks alike
-        mask = mk.data_ptr<uint8_t>();
+        mk = mask_bytes(*row_mask);
+        mask = static_cast<const uint8_t*>(mk.data_ptr());
         width = param.size(0) ? (size_t)(param.numel() / param.size(0)) : 1;
     }
     check_status(f3dgs_adam_step_rows((size_t)param.numel(), width, mask, param.data_ptr<float>(), g.data_ptr<float>(),
@@ -578,8 +585,8 @@ void AdamStepMulti(std::vector<torch::Tensor> params, std::vector<torch::Tensor>
     torch::Tensor mk;
     if (row_mask.has_value() && row_mask->defined()) {
         TORCH_CHECK(row_mask->is_cuda(), "adam_step_multi: the mask must be a HIP tensor");
-        mk = row_mask->to(torch::kUInt8).contiguous();
-        mask = mk.data_ptr<uint8_t>();
+        mk = mask_bytes(*row_mask);
+        mask = static_cast<const uint8_t*>(mk.data_ptr());
         rows = (size_t)mk.numel();
     }
     check_status(f3dgs_adam_step_multi((int)n, tab, beta1, beta2, eps, mask, rows, current_stream(params[0])), "adam_step_multi");

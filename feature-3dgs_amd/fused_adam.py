@@ -24,7 +24,8 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, visibility=None):
-        """`visibility` (optional, (P,) bool/uint8 HIP tensor, e.g. `radii > 0`): an EXTENSION beyond the reference -
+        """`visibility` (optional, (P,) HIP tensor: bool, uint8 or a wider integer such as `radii` itself - any non-zero
+        entry means visible): an EXTENSION beyond the reference -
         only those rows of every (P, ...) tensor are stepped, the others keep parameter and moments (torch.optim.Adam
         would still move a never-visible Gaussian by its decaying first moment).  Default: the reference's dense Adam."""
         loss = None

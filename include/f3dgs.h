@@ -450,6 +450,13 @@ int f3dgs_adam_step_rows(size_t n, size_t width, const uint8_t* row_mask, float*
  * foreach kernels, scene/gaussian_model.py:163-178): a table of up to F3DGS_ADAM_MAX_TENSORS entries, each with its own
  * learning rate and step count (torch keeps them per parameter); beta1 / beta2 / eps are shared.  `row_mask` (optional,
  * `rows` bytes): the visibility-masked variant of f3dgs_adam_step_rows, applied to every tensor whose `n` is a multiple of `rows`.
+ * The table carries no per-tensor flag: with a mask, EVERY entry whose `n` is a whole multiple of `rows` (n = 0 apart) is
+ * taken as `rows` rows of n / rows floats, also one that is not per-row data and only happens to have such a length; the
+ * others are stepped densely.  A caller who holds such a tensor steps it with f3dgs_adam_step instead (FusedAdam does:
+ * it puts a tensor into a masked table only if its first dimension is the mask's length).
+ * Errors (F3DGS_ERR_INVALID_ARGUMENT, nothing launched): n_tensors outside 0 .. F3DGS_ADAM_MAX_TENSORS, a null table, an
+ * entry with n > 0 and a null pointer or step < 1, a mask with rows == 0.  f3dgs_adam_step[_rows]: a null pointer with
+ * n > 0, step < 1, a mask whose width is 0 or does not divide n.
  */
 #define F3DGS_ADAM_MAX_TENSORS 16
 typedef struct {
