@@ -377,7 +377,7 @@ CountReadback* count_readback(hipStream_t s, bool may_create) {
 
 extern "C" {
 
-int f3dgs_version(void) { return 30800; }   // 3.8.0 (major * 10000 + minor * 100 + patch): 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
+int f3dgs_version(void) { return 30900; }   // 3.9.0 (major * 10000 + minor * 100 + patch): 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
 
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 
@@ -861,6 +861,42 @@ int f3dgs_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const fl
     if (!scratch && (weight || !text_normalized)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: scratch is null");
     HIP_TRY(launch_segment(C, H, W, Cout, Hs, Ws, K, feature_map, weight, bias, text, (flags & F3DGS_SEGMENT_ROUND_HALF) != 0,
                            text_normalized, labels, score, static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+// nullptr if the shape is served, else the reason
+static const char* feature_pca_unsupported(int C, long long HW, int stride, bool moments) {
+    if (C < 3) return "feature_pca: C = %d, at least 3 channels are needed for 3 components";
+    if (C > F3DGS_FEATURE_PCA_MAX_CHANNELS) return "feature_pca: C = %d beyond the limit of 4096 channels";
+    if (HW < 0 || HW > (1ll << 30)) return "feature_pca: C = %d: the map is too large";
+    if (moments && stride < 1) return "feature_pca: C = %d: stride < 1";
+    return nullptr;
+}
+
+size_t f3dgs_feature_pca_scratch_bytes(int C, long long HW, int stride) {
+    if (feature_pca_unsupported(C, HW, stride, true) || HW == 0) return 0;
+    return feature_pca_scratch_bytes(C, (size_t)HW, stride);
+}
+
+int f3dgs_feature_pca_moments(int C, long long HW, int stride, const float* feature_map, double* mean, double* cov, void* scratch,
+                              void* stream) {
+    if (const char* why = feature_pca_unsupported(C, HW, stride, true)) return fail(F3DGS_ERR_UNSUPPORTED, why, C);
+    if (HW == 0) return F3DGS_OK;
+    const long long n = (HW + stride - 1) / stride;
+    if (n < 3) return fail(F3DGS_ERR_UNSUPPORTED, "feature_pca: %lld samples (HW = %lld, stride = %d), at least 3 are needed", n, HW, stride);
+    if (!feature_map || !mean || !cov || !scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_moments: null pointer");
+    HIP_TRY(launch_feature_pca_moments(C, (size_t)HW, stride, feature_map, mean, cov, static_cast<char*>(scratch),
+                                       static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_feature_pca_project(int C, long long HW, const float* feature_map, const float* mean, const float* components,
+                              const float* lo, const float* hi, float* out, void* stream) {
+    if (const char* why = feature_pca_unsupported(C, HW, 1, false)) return fail(F3DGS_ERR_UNSUPPORTED, why, C);
+    if ((lo == nullptr) != (hi == nullptr)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_project: lo and hi go together");
+    if (HW == 0) return F3DGS_OK;
+    if (!feature_map || !mean || !components || !out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_project: null pointer");
+    HIP_TRY(launch_feature_pca_project(C, (size_t)HW, feature_map, mean, components, lo, hi, out, static_cast<hipStream_t>(stream)));
     return F3DGS_OK;
 }
 

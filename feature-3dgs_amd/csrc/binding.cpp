@@ -526,6 +526,50 @@ Segment(const torch::Tensor& feature_map, const torch::Tensor& text, int64_t Hs,
     return std::make_tuple(labels, score);
 }
 
+// PCA of a feature map (include/f3dgs.h: f3dgs_feature_pca_*).  feature_map (C,H,W) float32.  Returns (mean (C), cov (C,C)) float64.
+std::tuple<torch::Tensor, torch::Tensor> FeaturePcaMoments(const torch::Tensor& feature_map, int64_t stride) {
+    TORCH_CHECK(feature_map.is_cuda(), "feature_pca_moments: feature_map must live on a HIP device (no CPU path)");
+    TORCH_CHECK(feature_map.scalar_type() == torch::kFloat32 && feature_map.dim() == 3, "feature_pca_moments: feature_map (C,H,W) float32 expected");
+    TORCH_CHECK(stride >= 1 && stride <= (1ll << 30), "feature_pca_moments: bad stride");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(feature_map.device());
+    auto fm = feature_map.contiguous();
+    const int C = (int)fm.size(0);
+    const long long HW = fm.size(1) * fm.size(2);
+    auto o = fm.options().dtype(torch::kFloat64);
+    torch::Tensor mean = torch::empty({C}, o), cov = torch::empty({C, C}, o);
+    torch::Tensor scratch = torch::empty({(long long)f3dgs_feature_pca_scratch_bytes(C, HW, (int)stride)}, fm.options().dtype(torch::kByte));
+    check_status(f3dgs_feature_pca_moments(C, HW, (int)stride, fptr(fm), mean.data_ptr<double>(), cov.data_ptr<double>(),
+                                           scratch.data_ptr(), current_stream(fm)),
+                 "feature_pca_moments");
+    return std::make_tuple(mean, cov);
+}
+
+// mean (C), components (3,C) float32; lo / hi 0-dim float32 device tensors or None.  Returns (H,W,3) float32.
+torch::Tensor FeaturePcaProject(const torch::Tensor& feature_map, const torch::Tensor& mean, const torch::Tensor& components,
+                                const c10::optional<torch::Tensor>& lo, const c10::optional<torch::Tensor>& hi) {
+    TORCH_CHECK(feature_map.is_cuda(), "feature_pca_project: feature_map must live on a HIP device (no CPU path)");
+    TORCH_CHECK(feature_map.scalar_type() == torch::kFloat32 && feature_map.dim() == 3, "feature_pca_project: feature_map (C,H,W) float32 expected");
+    TORCH_CHECK(lo.has_value() == hi.has_value(), "feature_pca_project: lo and hi go together");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(feature_map.device());
+    auto fm = feature_map.contiguous();
+    const int C = (int)fm.size(0);
+    const long long H = fm.size(1), W = fm.size(2);
+    auto dev = [&](const torch::Tensor& t, long long numel, const char* what) {
+        TORCH_CHECK(t.is_cuda() && t.device() == fm.device() && t.scalar_type() == torch::kFloat32 && t.numel() == numel,
+                    "feature_pca_project: ", what, " must be ", numel, " float32 value(s) on the map's device");
+        return t.contiguous();
+    };
+    const torch::Tensor m = dev(mean, C, "mean"), comp = dev(components, 3ll * C, "components");
+    torch::Tensor l, h;
+    if (lo.has_value()) { l = dev(*lo, 1, "lo"); h = dev(*hi, 1, "hi"); }
+    torch::Tensor out = torch::empty({H, W, 3}, fm.options());
+    check_status(f3dgs_feature_pca_project(C, H * W, fptr(fm), m.data_ptr<float>(), comp.data_ptr<float>(),
+                                           lo.has_value() ? l.data_ptr<float>() : nullptr, lo.has_value() ? h.data_ptr<float>() : nullptr,
+                                           H * W ? out.data_ptr<float>() : nullptr, current_stream(fm)),
+                 "feature_pca_project");
+    return out;
+}
+
 // One byte per row, non-zero where the mask is: bool / uint8 masks as they are, wider types through `!= 0` (a cast to
 // uint8 would wrap: an int32 `radii` of 256 handed in as the mask would read as "not visible").
 static torch::Tensor mask_bytes(const torch::Tensor& row_mask) {
@@ -658,6 +702,10 @@ PYBIND11_MODULE(_C, m) {
           py::arg("opacity") = py::none());
     m.def("segment", &Segment, py::arg("feature_map"), py::arg("text"), py::arg("Hs"), py::arg("Ws"), py::arg("weight"), py::arg("bias"),
           py::arg("flags"), py::arg("want_score"));
+    m.def("feature_pca_moments", &FeaturePcaMoments, py::arg("feature_map"), py::arg("stride"));
+    m.def("feature_pca_project", &FeaturePcaProject, py::arg("feature_map"), py::arg("mean"), py::arg("components"),
+          py::arg("lo") = py::none(), py::arg("hi") = py::none());
+    m.attr("FEATURE_PCA_MAX_CHANNELS") = (int)F3DGS_FEATURE_PCA_MAX_CHANNELS;
     m.attr("SEGMENT_ROUND_HALF") = (int)F3DGS_SEGMENT_ROUND_HALF;
     m.attr("SEGMENT_TEXT_NORMALIZED") = (int)F3DGS_SEGMENT_TEXT_NORMALIZED;
     m.attr("SEGMENT_MAX_TEXTS") = (int)F3DGS_SEGMENT_MAX_TEXTS;

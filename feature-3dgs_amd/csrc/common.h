@@ -293,6 +293,13 @@ hipError_t launch_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, 
                           const float* bias, const float* text, bool round_half, bool text_normalized, int64_t* labels,
                           float* score, char* scratch, hipStream_t s);
 
+// feature_pca.hip
+size_t feature_pca_scratch_bytes(int C, size_t HW, int stride);
+hipError_t launch_feature_pca_moments(int C, size_t HW, int stride, const float* feature_map, double* mean, double* cov,
+                                      char* scratch, hipStream_t s);
+hipError_t launch_feature_pca_project(int C, size_t HW, const float* feature_map, const float* mean, const float* components,
+                                      const float* lo, const float* hi, float* out, hipStream_t s);
+
 // api.hip: sets the text f3dgs_last_error() returns (for the entry points defined in other files); returns `code`
 int report_error(int code, const char* msg);
 

@@ -429,6 +429,35 @@ int f3dgs_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const fl
                   float* score /* Hs*Ws or NULL */, void* scratch, void* stream /* hipStream_t */);
 
 /*
+ * PCA colour image of a feature map (render.py:38-53, feature_visualize_saving), in two calls around a C x C eigenproblem
+ * that is the caller's (feature_pca.py solves it with torch.linalg.eigh in float64).  The (C,HW) map is read by kernels only
+ * and nothing of size C*HW is allocated.
+ * f3dgs_feature_pca_moments: the samples are pixels 0, stride, 2 stride, ... of the flattened map, n = ceil(HW / stride) of
+ * them (the reference: stride 3), each divided by max(its L2 norm, 1e-12) in fp32 (F.normalize: a zero pixel stays zero).
+ * `mean` (C doubles) receives their mean and `cov` (C x C doubles, symmetric, both triangles written) the covariance
+ * sum (x - mean)(x - mean)^T / (n - 1).  The samples are centred BEFORE they are contracted (a first pass forms the mean), the
+ * contraction runs on v_mfma_f32_32x32x2_f32 over upper-triangle block pairs with the fp32 accumulator emptied into float64
+ * every 256 samples, and all other sums are float64.  No floating-point atomics: two calls give identical bits.
+ * `scratch`: f3dgs_feature_pca_scratch_bytes(C, HW, stride) bytes: 4 n for the norms, 8 C per 16384 samples for the partial
+ * sums, 12 C, and the float64 partial blocks of the contraction, min(ceil(n / 1024), max(1, 1024 / pairs)) x pairs x 32 KB with
+ * pairs = nb (nb + 1) / 2, nb = ceil(C / 64).  That last part follows C, not HW: at most 32 MB up to 2048 channels and 68 MB at
+ * 4096 (half of `cov` itself), a few per cent of a map of image size, but MORE than a small map of many channels (C = 512 at
+ * 36 x 48: 1.15 MB, the map 3.5 MB, `cov` 2 MB).  "Nothing of size C*HW" is a statement about maps that are larger than C x C.
+ * f3dgs_feature_pca_project: t_k(p) = (x_p / max(||x_p||, 1e-12) - mean) . components[k], k = 0, 1, 2, for EVERY pixel p in one
+ * pass; `mean` (C floats) and `components` (3 x C floats) are device pointers.  With `lo` / `hi` (device floats, both or
+ * neither) `out` (HW x 3 floats, pixel-major) receives clamp((t - lo) / (hi - lo), 0, 1), with both NULL the raw t.
+ * C < 3, C > F3DGS_FEATURE_PCA_MAX_CHANNELS, stride < 1, fewer than 3 samples or HW > 2^30: F3DGS_ERR_UNSUPPORTED.  HW == 0 is
+ * a no-op.  No host read, no memset, no allocation; every launch goes to `stream`: capturable.
+ */
+#define F3DGS_FEATURE_PCA_MAX_CHANNELS 4096
+size_t f3dgs_feature_pca_scratch_bytes(int C, long long HW, int stride);
+int f3dgs_feature_pca_moments(int C, long long HW, int stride, const float* feature_map, double* mean /* C */,
+                              double* cov /* C x C */, void* scratch, void* stream /* hipStream_t */);
+int f3dgs_feature_pca_project(int C, long long HW, const float* feature_map, const float* mean /* C */,
+                              const float* components /* 3 x C */, const float* lo, const float* hi /* device, or both NULL */,
+                              float* out /* HW x 3 */, void* stream /* hipStream_t */);
+
+/*
  * One torch.optim.Adam step (no weight decay, no amsgrad: the reference's configuration,
  * scene/gaussian_model.py:163-178) over one tensor of n floats, in place; `step` is the 1-based step count of that
  * tensor.  param / grad / exp_avg / exp_avg_sq are device pointers.
