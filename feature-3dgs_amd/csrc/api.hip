@@ -707,6 +707,9 @@ int f3dgs_backward(int P, int D, int M, int C, int R, const float* background, i
     if (!dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || (C > 0 && !dL_dsemantic_feature))
         return fail(F3DGS_ERR_INVALID_ARGUMENT, "null output");
     if (M > 0 && shs && !dL_dsh) return fail(F3DGS_ERR_INVALID_ARGUMENT, "dL_dsh is null");
+    // as the forward call: the SH gradient of degree D fills (D + 1)^2 coefficients of an M-coefficient row
+    if (shs && dL_dsh && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "SH degree %d needs %d coefficients, M = %d", D, (D + 1) * (D + 1), M);
     if (scales && (!dL_dscale || !dL_drot || !rotations)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "scale/rot grads null");
     if (!scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "scratch is null");
     if (misaligned16({shs, rotations, dL_dsh, dL_drot, dL_dconic, dL_dsemantic_feature, scratch}))

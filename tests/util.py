@@ -40,6 +40,120 @@ def precompute_optionals(scene: dict) -> dict:
     return sc
 
 
+# ---- general cameras: arbitrary rotation and position, fx != fy, any SH width ---------------------------------------
+# Views A-D have no zero or unit entry in the view rotation and a camera away from the origin; B and C have rectangular
+# pixels (fy / fx = 1 / pix_aspect).  E is the family of synth.make_camera (used with SH widths other than 16 only).
+VIEWS = {
+    "A": dict(yaw=17.0, pitch=-11.0, roll=23.0, campos=(0.7, -0.4, -1.3), fovx_deg=60.0, pix_aspect=1.0, znear=0.01, zfar=100.0),
+    "B": dict(yaw=-31.0, pitch=8.0, roll=-140.0, campos=(-2.0, 1.5, 0.6), fovx_deg=35.0, pix_aspect=2.0, znear=0.01, zfar=100.0),
+    "C": dict(yaw=5.0, pitch=29.0, roll=90.0, campos=(3.0, 0.2, -0.8), fovx_deg=100.0, pix_aspect=0.5, znear=0.5, zfar=20.0),
+    "D": dict(yaw=12.0, pitch=-3.0, roll=7.0, campos=(0.1, 0.1, 0.1), fovx_deg=60.0, pix_aspect=1.0, znear=0.01, zfar=100.0),
+    "E": dict(yaw=0.0, pitch=0.0, roll=0.0, campos=(0.0, 0.0, 0.0), fovx_deg=60.0, pix_aspect=1.0, znear=0.01, zfar=100.0),
+}
+DEGREE_OF_M = {1: 0, 4: 1, 5: 1, 9: 2, 16: 3}         # the largest SH degree M coefficients hold
+
+
+def view_rotation(yaw: float, pitch: float, roll: float) -> np.ndarray:
+    """World-to-camera rotation R = Rz(roll) Rx(pitch) Ry(yaw), fp64, angles in degrees; Ry as synth.make_camera writes it
+    (the camera looks along (sin yaw, 0, cos yaw))."""
+    import math
+    a, b, c = (math.radians(v) for v in (yaw, pitch, roll))
+    Ry = np.array([[math.cos(a), 0.0, -math.sin(a)], [0.0, 1.0, 0.0], [math.sin(a), 0.0, math.cos(a)]])
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, math.cos(b), -math.sin(b)], [0.0, math.sin(b), math.cos(b)]])
+    Rz = np.array([[math.cos(c), -math.sin(c), 0.0], [math.sin(c), math.cos(c), 0.0], [0.0, 0.0, 1.0]])
+    return Rz @ Rx @ Ry
+
+
+def general_camera(width: int, height: int, yaw=0.0, pitch=0.0, roll=0.0, campos=(0.0, 0.0, 0.0), fovx_deg=60.0,
+                   pix_aspect=1.0, znear=0.01, zfar=100.0) -> dict:
+    """The camera entries of a scene dict for a camera at `campos` (world) with world-to-camera rotation view_rotation(...),
+    composed as the reference's Camera composes them (scene/cameras.py:55-58): viewmatrix = W2C^T, projmatrix = view P^T,
+    campos = view^-1 [3, :3].  tanfovy = tanfovx H / W pix_aspect, so fy / fx = 1 / pix_aspect.  Also R, t (fp64)."""
+    import math
+    from synth import projection_matrix
+    fovx = math.radians(fovx_deg)
+    tanfovx = math.tan(fovx / 2)
+    tanfovy = tanfovx * height / width * pix_aspect
+    fovy = 2 * math.atan(tanfovy)
+    R = view_rotation(yaw, pitch, roll)
+    t = -R @ np.asarray(campos, np.float64)
+    w2c = np.eye(4)
+    w2c[:3, :3], w2c[:3, 3] = R, t
+    view_t = torch.from_numpy(w2c.astype(np.float32)).t()      # a transposed view of W2C, as the reference's Camera holds it:
+    campos = view_t.inverse()[3, :3].contiguous()              # the fp32 inverse rounds differently on a contiguous copy
+    view = view_t.contiguous()
+    proj = projection_matrix(znear, zfar, fovx, fovy).t().contiguous()
+    full = (view.unsqueeze(0).bmm(proj.unsqueeze(0))).squeeze(0).contiguous()
+    return dict(image_width=width, image_height=height, tanfovx=tanfovx, tanfovy=tanfovy, viewmatrix=view, projmatrix=full,
+                campos=campos, R=R, t=t, fovx=fovx, fovy=fovy)
+
+
+def general_view_scene(P: int, C: int, width: int, height: int, seed: int = 0, *, yaw=0.0, pitch=0.0, roll=0.0,
+                       campos=(0.0, 0.0, 0.0), fovx_deg=60.0, pix_aspect=1.0, znear=0.01, zfar=100.0, M=16, sh_degree=None,
+                       with_depth_grad=False, scale_lo=0.003, scale_hi=0.03, wide_scale=1.0) -> dict:
+    """synth.make_scene seen by a general camera.  make_scene's positions are camera-frame positions (its camera is the
+    identity): x and y are rescaled to the new frustum - which keeps the recipe's 2 % of splats beyond the frustum and 1 %
+    at the near plane -, carried to the world frame in fp64 (R^T (m - t)) and rounded to fp32.  `shs` keeps its first M
+    coefficients; sh_degree defaults to the largest M holds.  wide_scale multiplies the scales of the beyond-frustum
+    splats (the first 2 %): only a splat whose 3 sigma reach back into the image is visible with the 1.3x clamp active."""
+    import math
+    from synth import make_scene
+    if sh_degree is None:
+        sh_degree = DEGREE_OF_M[M]
+    sc = make_scene(P=P, C=C, width=width, height=height, seed=seed, sh_degree=sh_degree, with_depth_grad=with_depth_grad,
+                    scale_lo=scale_lo, scale_hi=scale_hi)
+    cam = general_camera(width, height, yaw, pitch, roll, campos, fovx_deg, pix_aspect, znear, zfar)
+    R, t = cam.pop("R"), cam.pop("t")
+    cam.pop("fovx"), cam.pop("fovy")
+    m = sc["means3D"].double().numpy().copy()
+    m[:, 0] *= cam["tanfovx"] / sc["tanfovx"]
+    m[:, 1] *= cam["tanfovy"] / sc["tanfovy"]
+    sc["means3D"] = torch.from_numpy(((m - t[None, :]) @ R).astype(np.float32)).contiguous()      # rows: R^T (m - t)
+    n_wide = int(0.02 * P)
+    if wide_scale != 1.0:
+        s = sc["scales"].clone()
+        s[:n_wide] *= wide_scale
+        sc["scales"] = s.contiguous()
+    sc["shs"] = sc["shs"][:, :M, :].contiguous()
+    sc["M"] = M
+    sc.update(cam)
+    return sc
+
+
+def view_scene(view: str, P: int, C: int, width: int, height: int, seed: int = 0, **kw) -> dict:
+    return general_view_scene(P, C, width, height, seed, **VIEWS[view], **kw)
+
+
+def input_conditions(scene: dict, radii, clamped) -> dict:
+    """What a general-view case must hold to be worth running (fp64 restatement of the view transform): visible Gaussians
+    with the 1.3x frustum clamp active in x / in y, Gaussians culled at the near plane, clamped SH colour channels."""
+    m = scene["means3D"].double().numpy()
+    pv = np.concatenate([m, np.ones((len(m), 1))], 1) @ scene["viewmatrix"].double().numpy()
+    z = pv[:, 2]
+    vis = np.asarray(radii).reshape(-1) > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rx, ry = np.abs(pv[:, 0] / z), np.abs(pv[:, 1] / z)
+    return dict(clamp_x=int((vis & (rx > 1.3 * scene["tanfovx"])).sum()), clamp_y=int((vis & (ry > 1.3 * scene["tanfovy"])).sum()),
+                near_culled=int((z <= 0.2).sum()), sh_clamped=int((np.asarray(clamped).reshape(-1, 3)[vis] != 0).sum()))
+
+
+def assert_input_conditions(scene: dict, radii, clamped, view: str = None, sh: bool = True):
+    c = input_conditions(scene, radii, clamped)
+    assert c["clamp_x"] >= 1 and c["clamp_y"] >= 1, f"no visible Gaussian with the frustum clamp active in x and in y: {c}"
+    assert c["near_culled"] >= 10, c
+    if sh:
+        assert c["sh_clamped"] >= 1, c
+    if view is not None and view != "E":
+        Rv = scene["viewmatrix"][:3, :3].numpy()
+        assert float(scene["campos"].norm()) > 0 and float(np.abs(scene["viewmatrix"][3, :3].numpy()).min()) > 0
+        assert (Rv != 0).all() and (np.abs(Rv) != 1).all()
+        fx = scene["image_width"] / (2 * scene["tanfovx"])
+        fy = scene["image_height"] / (2 * scene["tanfovy"])
+        if view in ("B", "C"):
+            assert abs(fx / fy - 1) > 0.1, (fx, fy)
+    return c
+
+
 def run_oracle(scene: dict, use_precomp_color=False, use_precomp_cov=False, backward=True):
     from oracle.oracle import Oracle, scene_kwargs
     o = Oracle()
@@ -99,7 +213,7 @@ def grad_report(name, got, want, rel=1e-3):
     return float(err.max() / scale), float(bad.mean())
 
 
-def _strict_compare(scene, pc=False, pv=False, channel_scale=None):
+def _strict_compare(scene, pc=False, pv=False, channel_scale=None, report=None):
     """HIP path vs the C++ oracle with the north-star bars: outputs <= 1e-4 abs, gradients <= 1e-3 rel
     (`|err| <= 1e-3 |g| + 1e-5 max|g|` for EVERY element and max err <= 1e-3 max|g|), after the pixels PROVEN to be
     threshold flips (refutil.flip_pixels: n_contrib / final-T evidence from both implementations) have been
@@ -107,7 +221,9 @@ def _strict_compare(scene, pc=False, pv=False, channel_scale=None):
 
     channel_scale (opt-in, one positive number s_c per feature channel): on top of those bars, feature-map channel c within
     1e-4 s_c at every non-flip pixel, and column c of dL_dsemantic_feature held to the gradient bars on its own - a channel
-    whose values are small next to the others' cannot hide an error in the whole-tensor maxima."""
+    whose values are small next to the others' cannot hide an error in the whole-tensor maxima.
+
+    report (opt-in, a dict): receives both sides' outputs and gradients and the oracle, for further assertions of the caller."""
     import refutil as ru
     W, H = scene["image_width"], scene["image_height"]
     npix = W * H
@@ -160,6 +276,8 @@ def _strict_compare(scene, pc=False, pv=False, channel_scale=None):
             mx, worst = ru.grad_errors(g_[:, c], w_[:, c])
             assert mx <= 1e-3, f"dL_dsemantic_feature channel {c}: max err / max|g| = {mx:.2e}"
             assert worst <= 1.0, f"dL_dsemantic_feature channel {c}: worst element {worst:.2f}x outside 1e-3*|g| + 1e-5*max|g|"
+    if report is not None:
+        report.update(got=got, got_g=got_g, want=want, want_g=want_g, oracle=o, nflip=nflip)
     return nflip
 
 
