@@ -570,6 +570,115 @@ torch::Tensor FeaturePcaProject(const torch::Tensor& feature_map, const torch::T
     return out;
 }
 
+// The viewer's render modes (include/f3dgs.h: f3dgs_view_*).  Shapes are view_modes.py's to check; here: device, dtype, sizes.
+static torch::Tensor view_f32(const torch::Tensor& t, const char* what) {
+    TORCH_CHECK(t.is_cuda(), "view_modes: ", what, " must live on a HIP device (no CPU path)");
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32, "view_modes: ", what, " must be float32");
+    return t.contiguous();
+}
+
+struct ViewCamera {
+    torch::Tensor proj, inv;
+    ViewCamera(const torch::Tensor& depth, const torch::Tensor& projection, const torch::Tensor& inv_full_proj) {
+        proj = view_f32(projection, "projection_matrix");
+        TORCH_CHECK(inv_full_proj.is_cuda() && inv_full_proj.scalar_type() == torch::kFloat64,
+                    "view_modes: the inverse of full_proj_transform must be float64 on a HIP device");
+        inv = inv_full_proj.contiguous();
+        TORCH_CHECK(proj.numel() == 16 && inv.numel() == 16, "view_modes: 4 x 4 matrices expected");
+        TORCH_CHECK(proj.device() == depth.device() && inv.device() == depth.device(), "view_modes: the matrices must live on the depth map's device");
+    }
+};
+
+// depth (H,W) float32.  Returns (H,W,3), or (3,H,W) with chw; with half the values are (n + 1) / 2.
+torch::Tensor ViewNormals(const torch::Tensor& depth, const torch::Tensor& projection, const torch::Tensor& inv_full_proj, bool chw,
+                          bool half) {
+    auto d = view_f32(depth, "depth");
+    TORCH_CHECK(d.dim() == 2, "view_normals: depth (H,W) expected");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(d.device());
+    const ViewCamera cam(d, projection, inv_full_proj);
+    const long long H = d.size(0), W = d.size(1);
+    TORCH_CHECK(H * W <= (1ll << 30), "view_normals: the frame is too large");
+    torch::Tensor out = chw ? torch::empty({3, H, W}, d.options()) : torch::empty({H, W, 3}, d.options());
+    check_status(f3dgs_view_normals((int)H, (int)W, fptr(d), cam.proj.data_ptr<float>(), cam.inv.data_ptr<double>(),
+                                    H * W ? out.data_ptr<float>() : nullptr,
+                                    (chw ? F3DGS_VIEW_NORMALS_CHW : 0) | (half ? F3DGS_VIEW_NORMALS_HALF : 0), current_stream(d)),
+                 "view_normals");
+    return out;
+}
+
+// image (Cn,H,W) float32.  Returns (field (H,W), minmax (2)).
+std::tuple<torch::Tensor, torch::Tensor> ViewGradient(const torch::Tensor& image) {
+    auto im = view_f32(image, "image");
+    TORCH_CHECK(im.dim() == 3 && im.size(0) >= 1, "view_gradient: image (Cn,H,W) with Cn >= 1 expected");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(im.device());
+    const long long H = im.size(1), W = im.size(2);
+    TORCH_CHECK(H * W <= (1ll << 30) && im.size(0) <= (1ll << 30), "view_gradient: the image is too large");
+    torch::Tensor out = torch::empty({H, W}, im.options()), minmax = torch::empty({2}, im.options());
+    check_status(f3dgs_view_gradient((int)im.size(0), (int)H, (int)W, fptr(im), H * W ? out.data_ptr<float>() : nullptr,
+                                     minmax.data_ptr<float>(), current_stream(im)),
+                 "view_gradient");
+    return std::make_tuple(out, minmax);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ViewCurvature(const torch::Tensor& depth, const torch::Tensor& projection,
+                                                       const torch::Tensor& inv_full_proj) {
+    auto d = view_f32(depth, "depth");
+    TORCH_CHECK(d.dim() == 2, "view_curvature: depth (H,W) expected");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(d.device());
+    const ViewCamera cam(d, projection, inv_full_proj);
+    const long long H = d.size(0), W = d.size(1);
+    TORCH_CHECK(H * W <= (1ll << 30), "view_curvature: the frame is too large");
+    torch::Tensor out = torch::empty({H, W}, d.options()), minmax = torch::empty({2}, d.options());
+    check_status(f3dgs_view_curvature((int)H, (int)W, fptr(d), cam.proj.data_ptr<float>(), cam.inv.data_ptr<double>(),
+                                      H * W ? out.data_ptr<float>() : nullptr, minmax.data_ptr<float>(), current_stream(d)),
+                 "view_curvature");
+    return std::make_tuple(out, minmax);
+}
+
+torch::Tensor ViewMinmax(const torch::Tensor& field) {
+    auto f = view_f32(field, "field");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(f.device());
+    torch::Tensor minmax = torch::empty({2}, f.options());
+    check_status(f3dgs_view_minmax(f.numel(), fptr(f), minmax.data_ptr<float>(), current_stream(f)), "view_minmax");
+    return minmax;
+}
+
+// field: any shape of HW float32 values; minmax (2), lut (L,3).  Returns ((3, *field.shape) float32 or None, (*field.shape, 3)
+// uint8 or None).
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>> ViewPalette(const torch::Tensor& field, const torch::Tensor& minmax,
+                                                                                    const torch::Tensor& lut, int64_t mode, bool want_float,
+                                                                                    bool want_u8) {
+    auto f = view_f32(field, "field");
+    auto mm = view_f32(minmax, "minmax"), l = view_f32(lut, "lut");
+    TORCH_CHECK(want_float || want_u8, "view_palette: no output asked for");
+    TORCH_CHECK(mm.numel() == 2 && l.dim() == 2 && l.size(1) == 3, "view_palette: minmax (2) and lut (L,3) expected");
+    TORCH_CHECK(mm.device() == f.device() && l.device() == f.device(), "view_palette: minmax and lut must live on the field's device");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(f.device());
+    const long long HW = f.numel();
+    c10::optional<torch::Tensor> of, ou;
+    std::vector<int64_t> sf{3}, su(f.sizes().begin(), f.sizes().end());
+    sf.insert(sf.end(), f.sizes().begin(), f.sizes().end());
+    su.push_back(3);
+    if (want_float) of = torch::empty(sf, f.options());
+    if (want_u8) ou = torch::empty(su, f.options().dtype(torch::kUInt8));
+    check_status(f3dgs_view_palette(HW, fptr(f), mm.data_ptr<float>(), l.data_ptr<float>(), (int)std::min<int64_t>(l.size(0), 1 << 20),
+                                    (int)mode, (want_float && HW) ? of->data_ptr<float>() : nullptr,
+                                    (want_u8 && HW) ? ou->data_ptr<uint8_t>() : nullptr, current_stream(f)),
+                 "view_palette");
+    return std::make_tuple(of, ou);
+}
+
+// image (3,H,W) float32 -> (H,W,3) uint8: clamp(c, 0, 1) * 255, truncated
+torch::Tensor ViewBytes(const torch::Tensor& image) {
+    auto im = view_f32(image, "image");
+    TORCH_CHECK(im.dim() == 3 && im.size(0) == 3, "view_bytes: image (3,H,W) expected");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(im.device());
+    torch::Tensor out = torch::empty({im.size(1), im.size(2), 3}, im.options().dtype(torch::kUInt8));
+    const long long HW = im.size(1) * im.size(2);
+    check_status(f3dgs_view_bytes(HW, fptr(im), HW ? out.data_ptr<uint8_t>() : nullptr, current_stream(im)), "view_bytes");
+    return out;
+}
+
 // One byte per row, non-zero where the mask is: bool / uint8 masks as they are, wider types through `!= 0` (a cast to
 // uint8 would wrap: an int32 `radii` of 256 handed in as the mask would read as "not visible").
 static torch::Tensor mask_bytes(const torch::Tensor& row_mask) {
@@ -706,6 +815,18 @@ PYBIND11_MODULE(_C, m) {
     m.def("feature_pca_project", &FeaturePcaProject, py::arg("feature_map"), py::arg("mean"), py::arg("components"),
           py::arg("lo") = py::none(), py::arg("hi") = py::none());
     m.attr("FEATURE_PCA_MAX_CHANNELS") = (int)F3DGS_FEATURE_PCA_MAX_CHANNELS;
+    m.def("view_normals", &ViewNormals, py::arg("depth"), py::arg("projection_matrix"), py::arg("inv_full_proj"), py::arg("chw") = false,
+          py::arg("half") = false);
+    m.def("view_gradient", &ViewGradient, py::arg("image"));
+    m.def("view_curvature", &ViewCurvature, py::arg("depth"), py::arg("projection_matrix"), py::arg("inv_full_proj"));
+    m.def("view_minmax", &ViewMinmax, py::arg("field"));
+    m.def("view_palette", &ViewPalette, py::arg("field"), py::arg("minmax"), py::arg("lut"), py::arg("mode"), py::arg("want_float") = true,
+          py::arg("want_u8") = false);
+    m.def("view_bytes", &ViewBytes, py::arg("image"));
+    m.attr("VIEW_TILE") = (int)F3DGS_VIEW_TILE;
+    m.attr("VIEW_PALETTE_MINMAX") = (int)F3DGS_VIEW_PALETTE_MINMAX;
+    m.attr("VIEW_PALETTE_MAX") = (int)F3DGS_VIEW_PALETTE_MAX;
+    m.attr("VIEW_PALETTE_MAX_ENTRIES") = (int)F3DGS_VIEW_PALETTE_MAX_ENTRIES;
     m.attr("SEGMENT_ROUND_HALF") = (int)F3DGS_SEGMENT_ROUND_HALF;
     m.attr("SEGMENT_TEXT_NORMALIZED") = (int)F3DGS_SEGMENT_TEXT_NORMALIZED;
     m.attr("SEGMENT_MAX_TEXTS") = (int)F3DGS_SEGMENT_MAX_TEXTS;

@@ -300,6 +300,17 @@ hipError_t launch_feature_pca_moments(int C, size_t HW, int stride, const float*
 hipError_t launch_feature_pca_project(int C, size_t HW, const float* feature_map, const float* mean, const float* components,
                                       const float* lo, const float* hi, float* out, hipStream_t s);
 
+// view_modes.hip
+hipError_t launch_view_normals(int H, int W, const float* depth, const float* proj, const double* inv, float* out, bool chw, bool half,
+                               hipStream_t s);
+hipError_t launch_view_gradient(int Cn, int H, int W, const float* image, float* out, float* minmax, hipStream_t s);
+hipError_t launch_view_curvature(int H, int W, const float* depth, const float* proj, const double* inv, float* out, float* minmax,
+                                 hipStream_t s);
+hipError_t launch_view_minmax(size_t n, const float* field, float* minmax, hipStream_t s);
+hipError_t launch_view_palette(size_t HW, const float* field, const float* minmax, const float* lut, int L, int mode, float* out_float,
+                               unsigned char* out_u8, hipStream_t s);
+hipError_t launch_view_bytes(size_t HW, const float* image, unsigned char* out, hipStream_t s);
+
 // api.hip: sets the text f3dgs_last_error() returns (for the entry points defined in other files); returns `code`
 int report_error(int code, const char* msg);
 

@@ -458,6 +458,56 @@ int f3dgs_feature_pca_project(int C, long long HW, const float* feature_map, con
                               float* out /* HW x 3 */, void* stream /* hipStream_t */);
 
 /*
+ * The viewer's render modes of a rendered view (utils/image_utils.py:60-161, render_net_image; callers view.py:25 and
+ * train.py:164): 'Normal', 'Edge', 'Curvature' and the palette-coloured frame of any one-channel map ('Depth' included).
+ * f3dgs_view_normals: depth_to_normal.  Per pixel (y,x) the world points of (y,x), (y+1,x) and (y,x+1) are formed as
+ * unproject_depth_map does - X = x / (W-1) * 2 - 1, Y = y / (H-1) * 2 - 1 (pixel indices, not centres), sdepth =
+ * (f1 d + f2) / (d + 1e-8) with f1 = proj[2][2], f2 = proj[3][2] of the reference's (transposed) projection_matrix, the row
+ * vector (X, Y, sdepth, 1) times `inv_full_proj`, the divide by w - and n = cross(p2 - p1, p3 - p1) / (|.| + 1e-8).  The
+ * unprojection and the two differences are FLOAT64 (the reference's float32 chain leaves errors of order 1 on some normals;
+ * the judge of this function is the reference's formula in float64), cross product and normalisation float32.  `proj`: 16
+ * floats, `inv_full_proj`: 16 DOUBLES, the inverse of full_proj_transform, row-major, both device pointers (view_modes.py:
+ * torch.linalg.inv in float64 on the map's device).  Points of row H and column W are the zero vector (the reference pads
+ * with zeros): the last row and column are computed against it and the corner pixel's normal is 0.  A depth of 0 is a value
+ * like any other.  `out`: H x W x 3 floats, or 3 x H x W with F3DGS_VIEW_NORMALS_CHW; with F3DGS_VIEW_NORMALS_HALF the value
+ * written is (n + 1) / 2, the image of the 'Normal' mode.  H == 1 or W == 1 (a division by zero in the reference):
+ * F3DGS_ERR_UNSUPPORTED.
+ * f3dgs_view_gradient: gradient_map.  image (Cn,H,W), any Cn >= 1; per channel gx, gy with the taps [[-1,0,1],[-2,0,2],
+ * [-1,0,1]] / 4 and their transpose, ZEROS outside the image; out (H x W) = sqrt(sum over channels of gx^2 + gy^2).
+ * f3dgs_view_curvature: f3dgs_view_gradient of the 3 x H x W, (n + 1) / 2 output of f3dgs_view_normals, bit for bit, in one
+ * kernel: the normal image never reaches memory.  (Outside the image that image is 0, not 0.5, as in the reference.)
+ * `minmax` of both (NULL, or two floats on the device): receives the minimum and the maximum of `out`.  f3dgs_view_minmax
+ * does the same for any field of n floats (a raw depth map).  The values are exactly those of the field (of torch.aminmax)
+ * for a field without NaN, -0 reported as +0; integer atomics only: two calls give identical bits.  Each of the three sets
+ * the slot to (+inf, -inf) by a one-thread launch in front of its kernel.
+ * f3dgs_view_palette: index -> row of `lut` (L x 3 floats, device; the library ships no palette).  F3DGS_VIEW_PALETTE_MINMAX
+ * is the reference's `colormap`: idx = rint((v - min) / (max - min) * (L-1)) in float32, halves to even (torch.round; L = 256
+ * there); max == min, 0/0 in the reference, gives index 0 everywhere.  F3DGS_VIEW_PALETTE_MAX is render.py:155-161
+ * (matplotlib's float call): idx = min(int(v / max * L), L-1), negative values index 0; max == 0 gives index 0.  A NaN
+ * indexes 0.  `minmax` is the two-float device slot.  `out_float` (3 x HW, or NULL) receives the colour, `out_u8` (HW x 3
+ * bytes, pixel-major, or NULL) what view.py:26 sends: clamp(c, 0, 1) * 255 truncated.  f3dgs_view_bytes is that last step for
+ * an image (3 x HW floats) that needs no palette.
+ * H * W (HW, n) > 2^30, L < 2, L > F3DGS_VIEW_PALETTE_MAX_ENTRIES: F3DGS_ERR_UNSUPPORTED.  H * W == 0 is a no-op.  No host
+ * read, no memset, no allocation; every launch goes to `stream`: capturable.  Workgroups cover F3DGS_VIEW_TILE^2 pixels.
+ */
+#define F3DGS_VIEW_TILE 16
+#define F3DGS_VIEW_NORMALS_CHW 0x1
+#define F3DGS_VIEW_NORMALS_HALF 0x2
+#define F3DGS_VIEW_PALETTE_MINMAX 0
+#define F3DGS_VIEW_PALETTE_MAX 1
+#define F3DGS_VIEW_PALETTE_MAX_ENTRIES 4096
+int f3dgs_view_normals(int H, int W, const float* depth, const float* proj /* 4 x 4 */, const double* inv_full_proj /* 4 x 4 */,
+                       float* out, int flags, void* stream /* hipStream_t */);
+int f3dgs_view_gradient(int Cn, int H, int W, const float* image, float* out /* H x W */, float* minmax /* 2, or NULL */,
+                        void* stream /* hipStream_t */);
+int f3dgs_view_curvature(int H, int W, const float* depth, const float* proj, const double* inv_full_proj, float* out /* H x W */,
+                         float* minmax /* 2, or NULL */, void* stream /* hipStream_t */);
+int f3dgs_view_minmax(long long n, const float* field, float* minmax /* 2 */, void* stream /* hipStream_t */);
+int f3dgs_view_palette(long long HW, const float* field, const float* minmax /* 2 */, const float* lut /* L x 3 */, int L, int mode,
+                       float* out_float /* 3 x HW, or NULL */, uint8_t* out_u8 /* HW x 3, or NULL */, void* stream /* hipStream_t */);
+int f3dgs_view_bytes(long long HW, const float* image /* 3 x HW */, uint8_t* out_u8 /* HW x 3 */, void* stream /* hipStream_t */);
+
+/*
  * One torch.optim.Adam step (no weight decay, no amsgrad: the reference's configuration,
  * scene/gaussian_model.py:163-178) over one tensor of n floats, in place; `step` is the 1-based step count of that
  * tensor.  param / grad / exp_avg / exp_avg_sq are device pointers.
