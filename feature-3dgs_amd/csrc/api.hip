@@ -808,6 +808,10 @@ int f3dgs_feature_l1(int C, int H, int W, int Cout, int Hg, int Wg, const float*
         return fail(F3DGS_ERR_INVALID_ARGUMENT, "without a decoder the ground truth must have C = %d channels, got %d", C, Cout);
     }
     if ((long long)Hg * Wg * (long long)(Cout > C ? Cout : C) >= (1ll << 40)) return fail(F3DGS_ERR_UNSUPPORTED, "too large");
+    // the decoder kernels read W rows, the resized map and the sign bytes - arrays carved from `scratch` at multiples of 16
+    // bytes - and write g_x with 16-byte accesses
+    if (weight && misaligned16({weight, scratch}))
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "with a decoder, weight and scratch must be 16-byte aligned (f3dgs.h, Alignment)");
     HIP_TRY(launch_feature_l1(C, H, W, Cout, Hg, Wg, feature_map, weight, bias, gt, loss, d_feature_map, d_weight, d_bias,
                               static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
     return F3DGS_OK;
@@ -832,6 +836,8 @@ int f3dgs_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const fl
         if (!scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "scratch is null");
         if (!feature_l1_decoder_supported(C))
             return fail(F3DGS_ERR_UNSUPPORTED, "decoder input width %d: supported are 32, 64, 128", C);
+        if (misaligned16({weight, scratch}))       // 16-byte reads of W rows and of the resized map in `scratch`
+            return fail(F3DGS_ERR_INVALID_ARGUMENT, "with a decoder, weight and scratch must be 16-byte aligned (f3dgs.h, Alignment)");
     } else if (Cout != C) {
         return fail(F3DGS_ERR_INVALID_ARGUMENT, "without a decoder the output has C = %d channels, got %d", C, Cout);
     }

@@ -438,8 +438,9 @@ fl_resize_backward_kernel(ResizeGeom g, int C, const float* __restrict__ GX, flo
     __shared__ float s_wx[64][RB_MAXT];
     __shared__ int s_nx[64];
     const int x0 = blockIdx.x * 64, y = blockIdx.y, cb = blockIdx.z * 32;
-    auto cand = [](int i, float scale, int out, int& lo, int& hi) { resize_cand(i, scale, out, lo, hi); };
-    auto build = [](int i, float scale, int in, int out, int* oo, float* ww) { return resize_build<RB_MAXT>(i, scale, in, out, oo, ww); };
+    // (any sizes: the loss may enlarge, and a one-row or one-column source feeds every output along that axis)
+    auto cand = [](int i, float scale, int out, int& lo, int& hi) { resize_cand<true>(i, scale, out, lo, hi); };
+    auto build = [](int i, float scale, int in, int out, int* oo, float* ww) { return resize_build<RB_MAXT, true>(i, scale, in, out, oo, ww); };
     int yo[RB_MAXT];
     float wy[RB_MAXT];
     const int ny = build(y, g.sy, g.H, g.Hg, yo, wy);           // uniform over the workgroup

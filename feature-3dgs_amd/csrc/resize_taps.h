@@ -29,19 +29,23 @@ __device__ __forceinline__ void taps(int o, float scale, int in, int& i0, int& i
     l0 = 1.0f - l1;
 }
 
-// candidate outputs of a source index i: outputs o whose taps can include i
+// candidate outputs of a source index i: outputs o whose taps can include i.
+// scale 0: out == 1 (only output 0 exists) or in == 1 (EVERY output reads source index 0, the only one) - both are "all
+// outputs, for source index 0".  ANY_SIZE = false is for callers that never enlarge (in >= out: the blend backward), where
+// scale 0 can only mean out == 1 and the last output is the constant 0.
+template <bool ANY_SIZE = false>
 __device__ __forceinline__ void resize_cand(int i, float scale, int out, int& lo, int& hi) {
-    if (scale <= 0.f) { lo = 0; hi = (i == 0) ? 0 : -1; return; }
+    if (scale <= 0.f) { lo = 0; hi = (i == 0) ? (ANY_SIZE ? out - 1 : 0) : -1; return; }
     lo = max(0, (int)floorf((float)(i - 1) / scale) - 1);
     hi = min(out - 1, (int)ceilf((float)(i + 1) / scale) + 1);
 }
 
 // The transposed resize along one axis: the (output, weight) list of source index i, outputs ascending, zero weights
 // dropped; returns the count, or -1 when it exceeds CAP.  Shrinking (in >= out) never needs more than two entries.
-template <int CAP>
+template <int CAP, bool ANY_SIZE = false>
 __device__ __forceinline__ int resize_build(int i, float scale, int in, int out, int* oo, float* ww) {
     int lo, hi, n = 0;
-    resize_cand(i, scale, out, lo, hi);
+    resize_cand<ANY_SIZE>(i, scale, out, lo, hi);
     for (int o = lo; o <= hi; o++) {
         int a0, a1;
         float l0, l1;

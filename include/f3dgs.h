@@ -37,6 +37,12 @@
  * not).  f3dgs_forward / f3dgs_backward return F3DGS_ERR_INVALID_ARGUMENT for
  * a misaligned pointer; the torch binding copies such a view first.  Image
  * planes may have any alignment (aligned ones take the vector path).
+ * The decoder kernels of f3dgs_feature_l1 / f3dgs_feature_decode read the
+ * rows of `weight` and the arrays they carve from `scratch` with 16-byte
+ * accesses: with a decoder (weight != NULL) both must be 16-byte aligned, and
+ * a misaligned one is refused with F3DGS_ERR_INVALID_ARGUMENT before anything
+ * is launched.  `feature_map`, `gt`, `bias` and the gradient outputs may have
+ * any (float) alignment; an aligned `d_feature_map` takes the vector stores.
  *
  * Status codes: 0 = ok, negative = error; f3dgs_last_error() returns a
  * thread-local human-readable message for the last failing call.
@@ -302,6 +308,7 @@ int f3dgs_backward(
  * d_feature_map (C,H,W), d_weight (Cout,C), d_bias (Cout): the gradients of that loss (upstream gradient 1; they
  * scale linearly).  With a decoder C must be 32, 64 or 128 (the contraction runs on the fp32 matrix pipe in
  * 32-channel blocks); other shapes return F3DGS_ERR_UNSUPPORTED.  `scratch`: f3dgs_feature_l1_scratch_bytes(...) bytes.
+ * With a decoder `weight` and `scratch` must be 16-byte aligned ("Alignment" above): F3DGS_ERR_INVALID_ARGUMENT otherwise.
  *
  * d_feature_map may be NULL: the dense (C,H,W) gradient - zeros at every pixel the resize does not sample, 8 of 9 when the
  * ground truth is a third of the image - is then not written.  The gradient at the LOSS's resolution stays in `scratch`
@@ -399,6 +406,7 @@ int f3dgs_edit_select(int P, int C, int K, const float* features, float* normali
  * is resized (bilinear, align_corners=True) to (Hg,Wg) and - if weight / bias are given - decoded by the 1x1 conv into
  * `out` (Cout,Hg,Wg), fp32 or (out_is_half != 0) IEEE fp16 as render.py stores it.  Without a decoder Cout must equal C.
  * With a decoder C must be 32, 64 or 128.  `scratch`: f3dgs_feature_decode_scratch_bytes(...) bytes (0 without a decoder).
+ * With a decoder `weight` and `scratch` must be 16-byte aligned ("Alignment" above): F3DGS_ERR_INVALID_ARGUMENT otherwise.
  */
 size_t f3dgs_feature_decode_scratch_bytes(int C, int Hg, int Wg, int has_decoder);
 int f3dgs_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,

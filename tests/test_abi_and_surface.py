@@ -95,6 +95,26 @@ def test_argument_validation_without_gpu():
     assert lib.f3dgs_feature_l1_lowres_grad(4, 4, 4, 4, 0, None) is None
 
 
+def test_feature_entry_points_refuse_misaligned_decoder_pointers_without_gpu():
+    """f3dgs_feature_l1 / f3dgs_feature_decode with a decoder: `weight` and `scratch` carry 16-byte accesses (include/f3dgs.h,
+    Alignment) and are refused off a 16-byte boundary by the argument checks - before any device work, so the addresses here
+    are never dereferenced."""
+    lib = ctypes.CDLL(_ensure_built())
+    lib.f3dgs_last_error.restype = ctypes.c_char_p
+    vp = ctypes.c_void_p
+    lib.f3dgs_feature_l1.argtypes = [ctypes.c_int] * 6 + [vp] * 10
+    lib.f3dgs_feature_decode.argtypes = [ctypes.c_int] * 6 + [vp] * 4 + [ctypes.c_int, vp, vp]
+    A = 0x10000                                    # a 16-byte aligned, never dereferenced address
+    for w_off, s_off in ((4, 0), (0, 4), (8, 8), (0, 1)):
+        rc = lib.f3dgs_feature_l1(32, 8, 8, 33, 4, 4, A, A + w_off, A, A, A, A, A, A, A + s_off, None)
+        assert rc == -1 and b"16-byte" in lib.f3dgs_last_error(), (w_off, s_off, rc)
+        rc = lib.f3dgs_feature_decode(32, 8, 8, 33, 4, 4, A, A + w_off, A, A, 0, A + s_off, None)
+        assert rc == -1 and b"16-byte" in lib.f3dgs_last_error(), (w_off, s_off, rc)
+    # the checks in front of it still answer first
+    assert lib.f3dgs_feature_l1(48, 8, 8, 33, 4, 4, A, A + 4, A, A, A, A, A, A, A, None) == -4        # F3DGS_ERR_UNSUPPORTED
+    assert lib.f3dgs_feature_decode(32, 8, 8, 33, 4, 4, A, A + 4, None, A, 0, A, None) == -1 and b"go together" in lib.f3dgs_last_error()
+
+
 def test_python_surface_matches_reference():
     _ensure_built()
     import diff_gaussian_rasterization as dgr

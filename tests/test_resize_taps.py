@@ -28,7 +28,8 @@ def taps(o, scale, n_in):
 
 def cand(i, scale, n_out):
     if scale <= 0:
-        return (0, 0 if i == 0 else -1)
+        return (0, n_out - 1 if i == 0 else -1)      # resize_cand<true>: out == 1, or in == 1 where every output reads source
+                                                           # index 0 (resize_cand<false>, in >= out only, is the same there)
     lo = max(0, int(np.floor(f32(i - 1) / scale)) - 1)
     hi = min(n_out - 1, int(np.ceil(f32(i + 1) / scale)) + 1)
     return lo, hi
@@ -69,6 +70,20 @@ def test_shrinking_needs_at_most_two_output_samples_per_source_index_and_the_lis
             assert [o for o, _ in lst] == sorted(o for o, _ in lst)
             col = np.zeros(n_out, np.float32)
             for o, w in lst:
+                col[o] = w
+            assert np.array_equal(col, M[:, i]), (n_in, n_out, i)
+
+
+def test_enlarging_lists_are_the_transpose_too():
+    """in < out (the loss's own transposed resize takes any size): the lists are still the columns of the forward matrix - a
+    one-element source (scale 0 with out > 1) included, where every output reads source index 0."""
+    for n_in, n_out in [(1, 2), (1, 7), (1, 12), (2, 3), (4, 64), (16, 40), (16, 56), (9, 257), (13, 43)]:
+        s = scale_of(n_in, n_out)
+        M = forward_matrix(n_in, n_out)
+        assert np.abs(M.sum(axis=1) - 1).max() <= 2e-7
+        for i in range(n_in):
+            col = np.zeros(n_out, np.float32)
+            for o, w in build(i, s, n_in, n_out):
                 col[o] = w
             assert np.array_equal(col, M[:, i]), (n_in, n_out, i)
 
