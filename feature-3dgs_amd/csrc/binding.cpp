@@ -444,6 +444,38 @@ torch::Tensor ImageLossBackward(const torch::Tensor& image, const torch::Tensor&
     return d_image;
 }
 
+// image-quality metrics of N view pairs (include/f3dgs.h: f3dgs_image_metrics).  image, gt: 4-D, float32 (N,C,H,W) for format
+// F3DGS_IMAGE_F32, uint8 (N,C,H,W) or (N,H,W,C) for the two uint8 formats, each side by itself.  Returns (l1, mse, psnr, ssim),
+// (N) float32 each; without want_ssim the last is empty and the windowed moments are not formed.
+static std::array<int, 4> image_metrics_dims(const torch::Tensor& t, int64_t format, const char* name) {
+    TORCH_CHECK(t.is_cuda(), "image_metrics: ", name, " must live on a HIP device (no CPU path)");
+    TORCH_CHECK(t.dim() == 4, "image_metrics: ", name, " must have 4 dimensions, got ", t.dim());
+    TORCH_CHECK(t.scalar_type() == (format == F3DGS_IMAGE_F32 ? torch::kFloat32 : torch::kByte), "image_metrics: ", name, " must be ",
+                format == F3DGS_IMAGE_F32 ? "float32" : "uint8", " for format ", format);
+    for (int i = 0; i < 4; i++) TORCH_CHECK(t.size(i) < (1ll << 31), "image_metrics: ", name, " is too large");
+    if (format == F3DGS_IMAGE_U8_INTERLEAVED) return {(int)t.size(0), (int)t.size(3), (int)t.size(1), (int)t.size(2)};
+    return {(int)t.size(0), (int)t.size(1), (int)t.size(2), (int)t.size(3)};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+ImageMetrics(const torch::Tensor& image, const torch::Tensor& gt, int64_t image_format, int64_t gt_format, int64_t flags, bool want_ssim) {
+    const auto d = image_metrics_dims(image, image_format, "image"), dg = image_metrics_dims(gt, gt_format, "gt");
+    TORCH_CHECK(d == dg, "image_metrics: image and gt shapes differ");
+    TORCH_CHECK(image.device() == gt.device(), "image_metrics: image and gt are on different devices");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(image.device());
+    const torch::Tensor im = image.contiguous(), g = gt.contiguous();
+    auto o = im.options().dtype(torch::kFloat32);
+    torch::Tensor l1 = torch::empty({d[0]}, o), mse = torch::empty({d[0]}, o), psnr = torch::empty({d[0]}, o);
+    torch::Tensor ssim = torch::empty({want_ssim ? d[0] : 0}, o);
+    if (d[0] == 0) return std::make_tuple(l1, mse, psnr, ssim);
+    torch::Tensor scratch = torch::empty({(long long)f3dgs_image_metrics_scratch_bytes(d[0], d[1], d[2], d[3])}, o.dtype(torch::kByte));
+    const int rc = f3dgs_image_metrics(d[0], d[1], d[2], d[3], im.data_ptr(), (int)image_format, g.data_ptr(), (int)gt_format, (int)flags,
+                                       l1.data_ptr<float>(), mse.data_ptr<float>(), psnr.data_ptr<float>(),
+                                       want_ssim ? ssim.data_ptr<float>() : nullptr, scratch.data_ptr(), current_stream(im));
+    check_status(rc, "image_metrics");
+    return std::make_tuple(l1, mse, psnr, ssim);
+}
+
 // language-guided selection (include/f3dgs.h: f3dgs_edit_select).  features (P, C) float32, contiguous and 16-byte aligned where
 // normalize_inplace asks for the write-back (edit.py copies other views and copies back); text (K, C).  Returns (mask (P),
 // score (P) or None, opacity_out like opacity or None).
@@ -806,6 +838,13 @@ PYBIND11_MODULE(_C, m) {
     m.attr("IMAGE_LOSS_L1_DSSIM") = (int)F3DGS_IMAGE_LOSS_L1_DSSIM;
     m.attr("IMAGE_LOSS_SSIM") = (int)F3DGS_IMAGE_LOSS_SSIM;
     m.attr("IMAGE_LOSS_SSIM_PER_IMAGE") = (int)F3DGS_IMAGE_LOSS_SSIM_PER_IMAGE;
+    m.def("image_metrics", &ImageMetrics, py::arg("image"), py::arg("gt"), py::arg("image_format"), py::arg("gt_format"), py::arg("flags"),
+          py::arg("want_ssim") = true);
+    m.attr("IMAGE_F32") = (int)F3DGS_IMAGE_F32;
+    m.attr("IMAGE_U8_PLANAR") = (int)F3DGS_IMAGE_U8_PLANAR;
+    m.attr("IMAGE_U8_INTERLEAVED") = (int)F3DGS_IMAGE_U8_INTERLEAVED;
+    m.attr("METRICS_QUANTIZE_IMAGE") = (int)F3DGS_METRICS_QUANTIZE_IMAGE;
+    m.attr("METRICS_QUANTIZE_GT") = (int)F3DGS_METRICS_QUANTIZE_GT;
     m.def("edit_select", &EditSelect, py::arg("features"), py::arg("text"), py::arg("positive_mask"), py::arg("first_positive"),
           py::arg("variant"), py::arg("threshold") = py::none(), py::arg("normalize_inplace") = false, py::arg("want_score") = false,
           py::arg("opacity") = py::none());

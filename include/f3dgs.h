@@ -363,6 +363,44 @@ int f3dgs_image_loss_backward(int N, int C, int H, int W, const float* image, co
                               const float* upstream, const void* scratch, float* d_image, void* stream);
 
 /*
+ * Image-quality metrics of N rendered views against their ground truth, forward only (the image half of evaluation:
+ * metrics.py:71-74 `ssim` and `psnr` per test view, train.py:210-239 `l1_loss` and `psnr`).  Per image n of the N x C x H x W
+ * batch, in one launch chain:
+ *   l1[n]   = mean |image - gt|                    (utils/loss_utils.py:17-18, per image)
+ *   mse[n]  = mean (image - gt)^2                  (utils/image_utils.py:20-21)
+ *   psnr[n] = 20 * log10(1 / sqrt(mse[n]))         (utils/image_utils.py:23-25: formed in fp32 from the fp32 mse; identical
+ *                                                   images give +inf, as the reference does)
+ *   ssim[n] = mean SSIM                            (utils/loss_utils.py:33-63 at window_size 11: the window, padding and
+ *                                                   constants of f3dgs_image_loss_forward)
+ * Each output is NULL or N floats on the device.  With ssim == NULL the windowed moments are not formed at all.
+ * `image` and `gt` choose their format independently:
+ *   F3DGS_IMAGE_F32             N x C x H x W fp32, contiguous; with F3DGS_METRICS_QUANTIZE_IMAGE / _GT in `flags` every value v
+ *                               is replaced by floor(clamp(v * 255 + 0.5, 0, 255)) / 255 as it is read - the value
+ *                               to_tensor(Image.open(...)) gives of the PNG that torchvision's save_image wrote of v
+ *                               (render.py:151-152; `mul(255).add_(0.5).clamp_(0, 255)`, the cast to uint8, `div(255)`: the
+ *                               same fp32 roundings in the same order; a NaN is cast to 0 and +-inf clamp).  Without the flag
+ *                               the values are taken as they are, NaN included.
+ *   F3DGS_IMAGE_U8_PLANAR       N x C x H x W uint8; the value is v / 255 (fp32 division, as to_tensor forms it)
+ *   F3DGS_IMAGE_U8_INTERLEAVED  N x H x W x C uint8, as PIL hands an image over
+ * A quantised fp32 side and the uint8 tensor torch's chain makes of it give bit-identical results.  Any N, C, H, W >= 1, images
+ * smaller than the window included; N == 0 is a no-op.  F3DGS_ERR_INVALID_ARGUMENT: bad sizes, an unknown format or flag, a
+ * quantize flag on a uint8 side, a NULL image, gt or scratch.  `scratch`: f3dgs_image_metrics_scratch_bytes(N, C, H, W) bytes
+ * (three partial sums per 64 x 16 tile; 0 for bad sizes), uninitialised.  Planes of any alignment; rows are read with 16-byte
+ * (fp32) or 4-byte (uint8 planar) loads when W % 4 == 0 and the base pointer is aligned to that.  Deterministic (partial sums
+ * reduced in a fixed order in fp64, no atomics); nothing is read back to the host, no memset is issued and both launches go
+ * to `stream`: capturable.
+ */
+#define F3DGS_IMAGE_F32 0
+#define F3DGS_IMAGE_U8_PLANAR 1
+#define F3DGS_IMAGE_U8_INTERLEAVED 2
+#define F3DGS_METRICS_QUANTIZE_IMAGE 0x1
+#define F3DGS_METRICS_QUANTIZE_GT 0x2
+size_t f3dgs_image_metrics_scratch_bytes(int N, int C, int H, int W);
+int f3dgs_image_metrics(int N, int C, int H, int W, const void* image, int image_format, const void* gt, int gt_format, int flags,
+                        float* l1 /* N */, float* mse /* N */, float* psnr /* N */, float* ssim /* N */, void* scratch,
+                        void* stream /* hipStream_t */);
+
+/*
  * Language-guided editing (gaussian_renderer/__init__.py:21-55, calculate_selection_score and
  * calculate_selection_score_delete; render_edit :131-148 calls them for every edited frame): which rows of the (P, C) fp32
  * feature table match the K text embeddings `text` (K x C fp32), in one pass over the table.  Per row f, in the reference's
