@@ -97,6 +97,14 @@ int fail(int code, const char* fmt, ...) {
 }  // namespace
 
 int f3dgs::report_error(int code, const char* msg) { return fail(code, "%s", msg); }
+int f3dgs::report_errorf(int code, const char* fmt, ...) {
+    char buf[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return report_error(code, buf);
+}
 
 namespace {
 

@@ -313,6 +313,9 @@ hipError_t launch_view_bytes(size_t HW, const float* image, unsigned char* out, 
 
 // api.hip: sets the text f3dgs_last_error() returns (for the entry points defined in other files); returns `code`
 int report_error(int code, const char* msg);
+int report_errorf(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // adam.hip
 void launch_adam_step(size_t n, float* p, const float* g, float* m, float* v, double lr, double b1, double b2, double eps,
@@ -363,6 +366,12 @@ void launch_tile_order(const uint32_t* tile_len, size_t tiles, uint32_t* order, 
 
 // ---- device helpers --------------------------------------------------------------------------------
 #if defined(__HIPCC__)
+// sum over the 64 lanes of a wave (all of them take part), in every lane
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
 // XCD-aware bijective remap of a linear workgroup id: workgroup b runs on XCD b % 8 (observed,
 // MI355X_MICROARCH.md), so give every XCD one contiguous run of tiles to keep neighbouring tiles
 // (which share splat records and feature vectors) behind the same L2.

@@ -19,8 +19,6 @@
 // are group reductions as well, so all rows of a wave are decided at once.  Rows with C % 4 != 0, unaligned pointers or
 // C > 2048 take edit_generic_kernel: scalar loads, the row re-read per text row (from cache), same arithmetic.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <hip/hip_fp16.h>
 
@@ -332,17 +330,6 @@ int pow2_at_least(int x) {
     return g;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-int bad(int code, const char* fmt, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return report_error(code, buf);
-}
-
 }  // namespace
 
 }  // namespace f3dgs
@@ -354,22 +341,23 @@ extern "C" {
 int f3dgs_edit_select(int P, int C, int K, const float* features, float* normalized_out, const float* text,
                       uint64_t positive_mask, int first_positive, int variant, int has_threshold, float threshold,
                       float* mask_out, float* score_out, const float* opacity_in, float* opacity_out, void* stream) {
-    if (P < 0 || P > (1 << 30) || C < 1 || K < 1) return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: bad sizes P=%d C=%d K=%d", P, C, K);
+    if (P < 0 || P > (1 << 30) || C < 1 || K < 1)
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: bad sizes P=%d C=%d K=%d", P, C, K);
     if (K > F3DGS_EDIT_MAX_TEXTS || (long long)K * C > F3DGS_EDIT_MAX_TEXT_ELEMENTS)
-        return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: K=%d C=%d beyond the limit of %d text rows and K*C <= %d", K, C,
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: K=%d C=%d beyond the limit of %d text rows and K*C <= %d", K, C,
                    F3DGS_EDIT_MAX_TEXTS, F3DGS_EDIT_MAX_TEXT_ELEMENTS);
     const int known = F3DGS_EDIT_DELETE | F3DGS_EDIT_TEXT_NORMALIZED | F3DGS_EDIT_FILL_UNSELECTED;
-    if (variant & ~known) return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: unknown variant bits 0x%x", variant & ~known);
-    if (positive_mask == 0) return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: empty positive mask");
+    if (variant & ~known) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: unknown variant bits 0x%x", variant & ~known);
+    if (positive_mask == 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: empty positive mask");
     if (K < 64 && (positive_mask >> K) != 0)
-        return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: positive mask has bits at or above K=%d", K);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: positive mask has bits at or above K=%d", K);
     if (first_positive < 0 || first_positive >= K || !((positive_mask >> first_positive) & 1))
-        return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: first_positive=%d is not in the positive mask", first_positive);
-    if (K == 1 && !has_threshold) return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: K=1 needs a threshold");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: first_positive=%d is not in the positive mask", first_positive);
+    if (K == 1 && !has_threshold) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: K=1 needs a threshold");
     if ((opacity_in == nullptr) != (opacity_out == nullptr))
-        return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: opacity_in and opacity_out go together (both or neither)");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: opacity_in and opacity_out go together (both or neither)");
     if (P == 0) return F3DGS_OK;
-    if (!features || !text || !mask_out) return bad(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: null pointer");
+    if (!features || !text || !mask_out) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "edit_select: null pointer");
 
     EditArgs a;
     a.P = P; a.C = C; a.K = K;
@@ -401,7 +389,7 @@ int f3dgs_edit_select(int P, int C, int K, const float* features, float* normali
         else hipLaunchKernelGGL(edit_rows_kernel<8>, grid, block, lds, s, a);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bad(F3DGS_ERR_HIP, "edit_select: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return report_errorf(F3DGS_ERR_HIP, "edit_select: %s", hipGetErrorString(e));
     return F3DGS_OK;
 }
 

@@ -29,12 +29,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // ---- K1: resize into pixel-major X; without a decoder (gt != nullptr) the L1 residual is taken here -------------
 // grid (ceil(N / 64), ceil(C / 32)); LDS tile [32 channels][64 pixels]
 __global__ void __launch_bounds__(256)

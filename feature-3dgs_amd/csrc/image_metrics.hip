@@ -3,59 +3,34 @@
 // Replaces the image half of the reference's evaluation (metrics.py:71-74 `ssim`, `psnr`; train.py:210-239 `l1_loss`, `psnr`):
 // per view pair five depthwise 11x11 convolutions, a squared-error pass and a host read.  Per image n of the batch
 //     l1[n] = mean |x - y|      mse[n] = mean (x - y)^2      psnr[n] = 20 log10(1 / sqrt(mse[n]))   (fp32, from the fp32 mse)
-//     ssim[n] = mean S          S as in image_loss.hip: Gaussian window 11, sigma 1.5, zero padding 5, C1 = 0.01^2, C2 = 0.03^2
+//     ssim[n] = mean S          S of ssim_tile.h: Gaussian window 11, sigma 1.5, zero padding 5, C1 = 0.01^2, C2 = 0.03^2
 // Forward only: no derivative maps.  Each side is fp32 planes, fp32 planes quantised to the 8-bit value a saved PNG holds, or
 // uint8 (planar or interleaved); an 8-bit side is staged as BYTES and widened with byte_to_unit, which is v / 255 bit for bit.
 // Stages:
-//   K1 im_tile_kernel     one 64 x 16 output tile of one plane per workgroup (the tile of image_loss.hip): x and y with a
-//                         5-pixel halo staged in LDS (zero outside the image); the 11-tap rows of the five moments by 208
-//                         threads, each sliding the window over a run of 8 pixels held in registers (18 staged values per
-//                         side instead of 88), into LDS; the 11-tap columns in registers; S, |d|, d^2 partial sums
+//   K1 im_tile_kernel     one 64 x 16 output tile of one plane per workgroup (the tile, fp32 staging, column pass and S of
+//                         ssim_tile.h): x and y with a 5-pixel halo staged in LDS (zero outside the image); the 11-tap rows
+//                         of the five moments by 208 threads, each sliding the window over a run of 8 pixels held in
+//                         registers (18 staged values per side instead of 88), into LDS; the 11-tap columns in registers;
+//                         S, |d|, d^2 partial sums
 //   K2 im_reduce_kernel   one workgroup per image: its partials in a fixed order (fp64) -> l1, mse, psnr, ssim
 // No atomics, no memset, no host read: two calls give the same bits and the call may be captured into a graph.
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "common.h"
+#include "ssim_tile.h"
 
 namespace f3dgs {
 
 namespace {
 
-constexpr int IM_R = 5;                   // window radius (window_size 11)
-constexpr int IM_TW = 64;                 // output tile: one column per lane in the column pass
-constexpr int IM_TH = 16;                 // four rows per wave
-constexpr int IM_SH = IM_TH + 2 * IM_R;   // staged rows
-constexpr int IM_SW = IM_TW + 16;         // staged columns: x0 - 8 .. x0 + 71, whole 4-element groups; the halo is 3 .. 76
-constexpr int IM_RUN = 8;                 // output pixels per thread of the row pass
-constexpr int IM_RUN_IN = IM_RUN + 2 * IM_R;   // staged values it reads: 18, from staged column 8 g + 3 on
-constexpr float IM_C1 = 0.01f * 0.01f, IM_C2 = 0.03f * 0.03f;
+using namespace ssim_tile;
+
+constexpr int RUN = 8;                // output pixels per thread of the row pass
+constexpr int RUN_IN = RUN + 2 * R;   // staged values it reads: 18, from staged column 8 g + 3 on
 
 // where a side's values come from
 constexpr int SRC_F32 = 0, SRC_F32_QUANT = 1, SRC_U8_PLANAR = 2, SRC_U8_INTERLEAVED = 3;
-
-struct Window {
-    float w[2 * IM_R + 1];
-};
-
-// The reference's 1-D window (loss_utils.py:24-26): the Gaussian in fp32 (torch.Tensor of Python floats), normalised in fp32.
-Window make_window() {
-    Window win;
-    float g[2 * IM_R + 1], sum = 0.f;
-    for (int i = 0; i <= 2 * IM_R; i++) {
-        g[i] = (float)exp(-(double)((i - IM_R) * (i - IM_R)) / (2.0 * 1.5 * 1.5));
-        sum += g[i];
-    }
-    for (int i = 0; i <= 2 * IM_R; i++) win.w[i] = g[i] / sum;
-    return win;
-}
-
-struct Geom {
-    int N, C, H, W;
-    int tiles_x, tiles_y;
-};
 
 struct Side {
     const void* p;
@@ -63,20 +38,14 @@ struct Side {
     int vec;       // whole 4-element groups may be loaded at once: W % 4 == 0 and the base aligned to 4 elements
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // b / 255 for an integer 0 <= b <= 255, bit for bit the fp32 quotient torch's `div(255)` forms (to_tensor): the product with the
 // rounded reciprocal is off by an ulp for 190 of the 256 values, one residual step corrects every one of them
 // (tests/test_image_metrics_cpu.py checks all 256 in exact arithmetic).  Three instructions instead of a division per tap.
 __device__ __forceinline__ float byte_to_unit(float b) {
-    constexpr float R = 1.0f / 255.0f;
-    const float q = __fmul_rn(b, R);
+    constexpr float RCP = 1.0f / 255.0f;
+    const float q = __fmul_rn(b, RCP);
     const float e = __fmaf_rn(-q, 255.0f, b);
-    return __fmaf_rn(e, R, q);
+    return __fmaf_rn(e, RCP, q);
 }
 
 // What `mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8)` makes of v (torchvision's save_image): two roundings, never one
@@ -104,11 +73,11 @@ __device__ __forceinline__ uint32_t load_byte(const Side& sd, const Geom& g, int
 
 // Stage the tile of one side with its halo as bytes, four to a dword, zeros outside the image.
 __device__ __forceinline__ void stage_bytes(unsigned char* s, const Side& sd, const Geom& g, int plane, int x0, int y0) {
-    constexpr int GROUPS = IM_SW / 4;
+    constexpr int GROUPS = SW / 4;
     uint32_t* const out = reinterpret_cast<uint32_t*>(s);
-    for (int i = threadIdx.x; i < IM_SH * GROUPS; i += 256) {
+    for (int i = threadIdx.x; i < SH * GROUPS; i += 256) {
         const int r = i / GROUPS, j = i - r * GROUPS;
-        const int gy = y0 - IM_R + r, gx = x0 - 8 + 4 * j;
+        const int gy = y0 - R + r, gx = x0 - 8 + 4 * j;
         uint32_t pack = 0;
         if (gy >= 0 && gy < g.H) {
             if (sd.vec && gx >= 0 && gx + 3 < g.W && sd.src != SRC_U8_INTERLEAVED) {
@@ -129,40 +98,22 @@ __device__ __forceinline__ void stage_bytes(unsigned char* s, const Side& sd, co
     }
 }
 
-// The same tile as fp32 (an unquantised fp32 side)
-__device__ __forceinline__ void stage_floats(unsigned char* s, const Side& sd, const Geom& g, int plane, int x0, int y0) {
-    const float* const src = static_cast<const float*>(sd.p) + (size_t)plane * g.H * g.W;
-    float* const out = reinterpret_cast<float*>(s);
-    if (sd.vec) {
-        constexpr int GROUPS = IM_SW / 4;
-        for (int i = threadIdx.x; i < IM_SH * GROUPS; i += 256) {
-            const int r = i / GROUPS, j = 4 * (i - r * GROUPS);
-            const int gy = y0 - IM_R + r, gx = x0 - 8 + j;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) v = *reinterpret_cast<const float4*>(src + (size_t)gy * g.W + gx);
-            *reinterpret_cast<float4*>(out + r * IM_SW + j) = v;
-        }
-    } else {
-        for (int i = threadIdx.x; i < IM_SH * IM_SW; i += 256) {
-            const int r = i / IM_SW, j = i - r * IM_SW;
-            const int gy = y0 - IM_R + r, gx = x0 - 8 + j;
-            const bool in = gy >= 0 && gy < g.H && gx >= 0 && gx < g.W;
-            out[i] = in ? src[(size_t)gy * g.W + gx] : 0.f;
-        }
-    }
-}
-
+// The same tile as fp32 (an unquantised fp32 side), or as bytes
 template <bool BYTES>
 __device__ __forceinline__ void stage(unsigned char* s, const Side& sd, const Geom& g, int plane, int x0, int y0) {
-    if constexpr (BYTES) stage_bytes(s, sd, g, plane, x0, y0);
-    else stage_floats(s, sd, g, plane, x0, y0);
+    if constexpr (BYTES) {
+        stage_bytes(s, sd, g, plane, x0, y0);
+    } else {
+        const float* const src[1] = {static_cast<const float*>(sd.p) + (size_t)plane * g.H * g.W};
+        stage_tile<1>(*reinterpret_cast<float(*)[1][SH][SW]>(s), src, g, x0, y0, sd.vec != 0);
+    }
 }
 
 // The 18 staged values of row r from staged column 8 g + 3 on
 template <bool BYTES>
-__device__ __forceinline__ void load_run(const unsigned char* s, int r, int g, float (&v)[IM_RUN_IN]) {
+__device__ __forceinline__ void load_run(const unsigned char* s, int r, int g, float (&v)[RUN_IN]) {
     if constexpr (BYTES) {
-        const uint2* const p = reinterpret_cast<const uint2*>(s + r * IM_SW + IM_RUN * g);      // (8-byte aligned: IM_SW % 8 == 0)
+        const uint2* const p = reinterpret_cast<const uint2*>(s + r * SW + RUN * g);      // (8-byte aligned: SW % 8 == 0)
         uint32_t d[6];
 #pragma unroll
         for (int j = 0; j < 3; j++) {
@@ -171,13 +122,13 @@ __device__ __forceinline__ void load_run(const unsigned char* s, int r, int g, f
             d[2 * j + 1] = u.y;
         }
 #pragma unroll
-        for (int i = 0; i < IM_RUN_IN; i++) {
-            const int e = i + 8 - IM_R;
+        for (int i = 0; i < RUN_IN; i++) {
+            const int e = i + 8 - R;
             v[i] = byte_to_unit((float)((d[e >> 2] >> (8 * (e & 3))) & 255u));
         }
     } else {
         // whole 16-byte groups from staged column 8 g on: single dwords at this lane stride would meet on four banks
-        const float4* const p = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(s) + r * IM_SW + IM_RUN * g);
+        const float4* const p = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(s) + r * SW + RUN * g);
         float f[24];
 #pragma unroll
         for (int j = 0; j < 6; j++) {
@@ -185,21 +136,21 @@ __device__ __forceinline__ void load_run(const unsigned char* s, int r, int g, f
             f[4 * j] = u.x; f[4 * j + 1] = u.y; f[4 * j + 2] = u.z; f[4 * j + 3] = u.w;
         }
 #pragma unroll
-        for (int i = 0; i < IM_RUN_IN; i++) v[i] = f[i + 8 - IM_R];
+        for (int i = 0; i < RUN_IN; i++) v[i] = f[i + 8 - R];
     }
 }
 
 template <bool BYTES>
 __device__ __forceinline__ float staged_value(const unsigned char* s, int r, int c) {
-    if constexpr (BYTES) return byte_to_unit((float)s[r * IM_SW + c]);
-    else return reinterpret_cast<const float*>(s)[r * IM_SW + c];
+    if constexpr (BYTES) return byte_to_unit((float)s[r * SW + c]);
+    else return reinterpret_cast<const float*>(s)[r * SW + c];
 }
 
 template <bool XB, bool YB>
 struct TileLds {
-    alignas(16) unsigned char sx[IM_SH * IM_SW * (XB ? 1 : 4)];      // x with halo: bytes, or fp32
-    alignas(16) unsigned char sy[IM_SH * IM_SW * (YB ? 1 : 4)];
-    alignas(16) float h[5][IM_SH][IM_TW];                            // 11-tap rows of x, y, x^2, y^2, xy
+    alignas(16) unsigned char sx[SH * SW * (XB ? 1 : 4)];      // x with halo: bytes, or fp32
+    alignas(16) unsigned char sy[SH * SW * (YB ? 1 : 4)];
+    alignas(16) float h[5][SH][TW];                            // 11-tap rows of x, y, x^2, y^2, xy
     float red[3][4];
 };
 
@@ -210,38 +161,36 @@ __global__ void __launch_bounds__(256)
 im_tile_kernel(Geom g, Window win, Side sx, Side sy, int want_ssim, float* __restrict__ part) {
     __shared__ TileLds<XB, YB> L;
     const int b = blockIdx.x;
-    const int tiles = g.tiles_x * g.tiles_y;
-    const int plane = b / tiles, t = b - plane * tiles;
-    const int ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
-    const int x0 = tx * IM_TW, y0 = ty * IM_TH;
+    const TilePos tp = tile_pos(g, b);
+    const int plane = tp.plane, x0 = tp.x0, y0 = tp.y0;
     stage<XB>(L.sx, sx, g, plane, x0, y0);
     stage<YB>(L.sy, sy, g, plane, x0, y0);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int rb = w * (IM_TH / 4);
+    const int rb = w * (TH / 4);
     float ssum = 0.f;
     if (want_ssim) {          // (the same in every thread)
         // rows: thread (r, run) slides the 11 taps along x over 8 pixels of staged row r, for the five moments
-        if (threadIdx.x < IM_SH * (IM_TW / IM_RUN)) {
+        if (threadIdx.x < SH * (TW / RUN)) {
             const int r = threadIdx.x >> 3, run = threadIdx.x & 7;
-            float xv[IM_RUN_IN], yv[IM_RUN_IN];
+            float xv[RUN_IN], yv[RUN_IN];
             load_run<XB>(L.sx, r, run, xv);
             load_run<YB>(L.sy, r, run, yv);
-            float acc[5][IM_RUN];
+            float acc[5][RUN];
 #pragma unroll
             for (int q = 0; q < 5; q++)
 #pragma unroll
-                for (int o = 0; o < IM_RUN; o++) acc[q][o] = 0.f;
+                for (int o = 0; o < RUN; o++) acc[q][o] = 0.f;
             // input-major: every product is formed once; each output still takes its taps in the order k = 0 .. 10
 #pragma unroll
-            for (int i = 0; i < IM_RUN_IN; i++) {
+            for (int i = 0; i < RUN_IN; i++) {
                 const float x = xv[i], y = yv[i];
                 const float xx = x * x, yy = y * y, xy = x * y;
 #pragma unroll
-                for (int o = 0; o < IM_RUN; o++) {
+                for (int o = 0; o < RUN; o++) {
                     const int k = i - o;
-                    if (k >= 0 && k <= 2 * IM_R) {
+                    if (k >= 0 && k <= 2 * R) {
                         const float wk = win.w[k];
                         acc[0][o] = fmaf(wk, x, acc[0][o]);
                         acc[1][o] = fmaf(wk, y, acc[1][o]);
@@ -253,7 +202,7 @@ im_tile_kernel(Geom g, Window win, Side sx, Side sy, int want_ssim, float* __res
             }
 #pragma unroll
             for (int q = 0; q < 5; q++) {
-                float4* const dst = reinterpret_cast<float4*>(&L.h[q][r][IM_RUN * run]);
+                float4* const dst = reinterpret_cast<float4*>(&L.h[q][r][RUN * run]);
                 dst[0] = make_float4(acc[q][0], acc[q][1], acc[q][2], acc[q][3]);
                 dst[1] = make_float4(acc[q][4], acc[q][5], acc[q][6], acc[q][7]);
             }
@@ -261,44 +210,18 @@ im_tile_kernel(Geom g, Window win, Side sx, Side sy, int want_ssim, float* __res
         __syncthreads();
 
         // columns: this wave's four output rows, 11 taps along y, in registers
-        float acc[IM_TH / 4][5];
+        float acc[TH / 4][5];
+        column_pass<5>(L.h, win, rb, lane, acc);
 #pragma unroll
-        for (int i = 0; i < IM_TH / 4; i++)
-#pragma unroll
-            for (int q = 0; q < 5; q++) acc[i][q] = 0.f;
-#pragma unroll
-        for (int j = 0; j < IM_TH / 4 + 2 * IM_R; j++) {
-            float v[5];
-#pragma unroll
-            for (int q = 0; q < 5; q++) v[q] = L.h[q][rb + j][lane];
-#pragma unroll
-            for (int i = 0; i < IM_TH / 4; i++) {
-                const int k = j - i;
-                if (k >= 0 && k <= 2 * IM_R) {
-#pragma unroll
-                    for (int q = 0; q < 5; q++) acc[i][q] = fmaf(win.w[k], v[q], acc[i][q]);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < IM_TH / 4; i++) {
-            if (x0 + lane < g.W && y0 + rb + i < g.H) {
-                const float mu1 = acc[i][0], mu2 = acc[i][1];
-                // the reference's order of operations (loss_utils.py:44-58)
-                const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
-                const float s1 = acc[i][2] - mu1_sq, s2 = acc[i][3] - mu2_sq, s12 = acc[i][4] - mu1_mu2;
-                const float A1 = 2.f * mu1_mu2 + IM_C1, A2 = 2.f * s12 + IM_C2;
-                const float B1 = mu1_sq + mu2_sq + IM_C1, B2 = s1 + s2 + IM_C2;
-                ssum += (A1 * A2) / (B1 * B2);
-            }
-        }
+        for (int i = 0; i < TH / 4; i++)
+            if (x0 + lane < g.W && y0 + rb + i < g.H) ssum += ssim_point(acc[i]).S;
     }
 
     float lsum = 0.f, msum = 0.f;
 #pragma unroll
-    for (int i = 0; i < IM_TH / 4; i++) {
+    for (int i = 0; i < TH / 4; i++) {
         if (x0 + lane < g.W && y0 + rb + i < g.H) {
-            const float d = staged_value<XB>(L.sx, rb + i + IM_R, lane + 8) - staged_value<YB>(L.sy, rb + i + IM_R, lane + 8);
+            const float d = staged_value<XB>(L.sx, rb + i + R, lane + 8) - staged_value<YB>(L.sy, rb + i + R, lane + 8);
             lsum += fabsf(d);
             msum = fmaf(d, d, msum);
         }
@@ -308,19 +231,7 @@ im_tile_kernel(Geom g, Window win, Side sx, Side sy, int want_ssim, float* __res
     msum = wave_sum(msum);
     if (lane == 0) { L.red[0][w] = ssum; L.red[1][w] = lsum; L.red[2][w] = msum; }
     __syncthreads();
-    if (threadIdx.x < 3) {
-        const float* const v = L.red[threadIdx.x];
-        part[(size_t)threadIdx.x * gridDim.x + b] = (v[0] + v[1]) + (v[2] + v[3]);
-    }
-}
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();            // (sh is re-used from one call to the next)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    if (threadIdx.x < 3) part[(size_t)threadIdx.x * gridDim.x + b] = four_wave_sum(L.red[threadIdx.x]);
 }
 
 // One workgroup per image: every thread sums a fixed strided set of the image's partials in fp64, then a fixed tree; thread 0
@@ -351,30 +262,13 @@ im_reduce_kernel(int per_image_blocks, size_t blocks, double inv_chw, int want_s
     }
 }
 
-size_t metric_blocks(int N, int C, int H, int W) {
-    return (size_t)N * C * ((W + IM_TW - 1) / IM_TW) * ((H + IM_TH - 1) / IM_TH);
-}
-
-bool bad_sizes(int N, int C, int H, int W) {
-    return N <= 0 || C <= 0 || H <= 0 || W <= 0 || (long long)N * C * H * W >= (1ll << 40) ||
-           (long long)N * C * ((W + IM_TW - 1) / IM_TW) * ((H + IM_TH - 1) / IM_TH) >= (1ll << 31);
-}
-
-int bad(int code, const char* fmt, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return report_error(code, buf);
-}
-
 // 0 on success; the side's description for the kernels
 int make_side(const void* p, int format, bool quant, int W, const char* name, Side* out) {
     if (format != F3DGS_IMAGE_F32 && format != F3DGS_IMAGE_U8_PLANAR && format != F3DGS_IMAGE_U8_INTERLEAVED)
-        return bad(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: unknown format %d of %s", format, name);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: unknown format %d of %s", format, name);
     if (quant && format != F3DGS_IMAGE_F32)
-        return bad(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: quantize flag on the uint8 side %s (it holds 8-bit values already)", name);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT,
+                             "image_metrics: quantize flag on the uint8 side %s (it holds 8-bit values already)", name);
     out->p = p;
     out->src = format == F3DGS_IMAGE_F32 ? (quant ? SRC_F32_QUANT : SRC_F32)
                                          : (format == F3DGS_IMAGE_U8_PLANAR ? SRC_U8_PLANAR : SRC_U8_INTERLEAVED);
@@ -399,27 +293,25 @@ extern "C" {
 size_t f3dgs_image_metrics_scratch_bytes(int N, int C, int H, int W) {
     if (bad_sizes(N, C, H, W)) return 0;
     Carver c(nullptr);
-    c.take<float>(3 * metric_blocks(N, C, H, W));
+    c.take<float>(3 * (size_t)tile_blocks(N, C, H, W));
     return c.total();
 }
 
 int f3dgs_image_metrics(int N, int C, int H, int W, const void* image, int image_format, const void* gt, int gt_format, int flags,
                         float* l1, float* mse, float* psnr, float* ssim, void* scratch, void* stream) {
     if (N == 0) return F3DGS_OK;
-    if (bad_sizes(N, C, H, W)) return bad(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: bad sizes N=%d C=%d H=%d W=%d", N, C, H, W);
+    if (bad_sizes(N, C, H, W))
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: bad sizes N=%d C=%d H=%d W=%d", N, C, H, W);
     if (flags & ~(F3DGS_METRICS_QUANTIZE_IMAGE | F3DGS_METRICS_QUANTIZE_GT))
-        return bad(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: unknown flags 0x%x", flags);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: unknown flags 0x%x", flags);
     Side sx, sy;
     if (make_side(image, image_format, (flags & F3DGS_METRICS_QUANTIZE_IMAGE) != 0, W, "image", &sx) != F3DGS_OK ||
         make_side(gt, gt_format, (flags & F3DGS_METRICS_QUANTIZE_GT) != 0, W, "gt", &sy) != F3DGS_OK)
         return F3DGS_ERR_INVALID_ARGUMENT;
-    if (!image || !gt || !scratch) return bad(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: null pointer");
+    if (!image || !gt || !scratch) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "image_metrics: null pointer");
     if (!l1 && !mse && !psnr && !ssim) return F3DGS_OK;
-    Geom g;
-    g.N = N; g.C = C; g.H = H; g.W = W;
-    g.tiles_x = (W + IM_TW - 1) / IM_TW;
-    g.tiles_y = (H + IM_TH - 1) / IM_TH;
-    const size_t nblocks = metric_blocks(N, C, H, W);
+    const Geom g = make_geom(N, C, H, W);
+    const size_t nblocks = (size_t)tile_blocks(N, C, H, W);
     const int blocks = (int)nblocks;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     float* const part = Carver(static_cast<char*>(scratch)).take<float>(3 * nblocks);
@@ -432,7 +324,7 @@ int f3dgs_image_metrics(int N, int C, int H, int W, const void* image, int image
     hipLaunchKernelGGL(im_reduce_kernel, dim3(N), dim3(256), 0, s, blocks / N, nblocks, 1.0 / ((double)C * H * W), want_ssim, part,
                        l1, mse, psnr, ssim);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bad(F3DGS_ERR_HIP, "image_metrics: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return report_errorf(F3DGS_ERR_HIP, "image_metrics: %s", hipGetErrorString(e));
     return F3DGS_OK;
 }
 

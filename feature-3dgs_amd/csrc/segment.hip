@@ -78,9 +78,7 @@ __global__ void __launch_bounds__(256) seg_text_kernel(int K, int Kpad, int Cout
     const float* t = text + (size_t)k * Cout;
     float ss = 0.f;
     for (int c = lane; c < Cout; c += 64) ss = fmaf(t[c], t[c], ss);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
-    const float n = sqrtf(ss);
+    const float n = sqrtf(wave_sum(ss));
     for (int c = lane; c < Cout; c += 64) o[c] = t[c] / n;
 }
 

@@ -109,6 +109,46 @@ def test_random_images_against_the_oracle_and_the_torch_ops(shape):
     assert err_fused <= 2 * err_torch + 1e-6 * float(ref["grad_loss"].abs().max()), (err_fused, err_torch)
 
 
+# (H, W) at the window's and the tile's edges: smaller than the 5-pixel halo, the 11-tap window exactly, the 64 x 16 tile exactly,
+# one more and one fewer in both directions, odd sizes inside one tile column and across three.  Two (N, C) per shape; together
+# every pair of N in {1, 3} and C in {1, 3, 4} occurs.
+_EDGE_CASES = [(1, 1, (1, 1)), (1, 1, (3, 4)), (5, 5, (1, 3)), (5, 5, (3, 1)), (11, 11, (1, 4)), (11, 11, (3, 3)),
+               (16, 64, (1, 1)), (16, 64, (3, 4)), (17, 65, (1, 3)), (17, 65, (3, 1)), (15, 63, (1, 4)), (15, 63, (3, 3)),
+               (37, 53, (1, 1)), (37, 53, (3, 4)), (33, 129, (1, 3)), (33, 129, (3, 1))]
+
+
+@pytest.mark.parametrize("H,W,nc", _EDGE_CASES, ids=[f"{h}x{w}-n{nc[0]}c{nc[1]}" for h, w, nc in _EDGE_CASES])
+def test_tile_and_window_edges_against_the_oracle(H, W, nc):
+    img, gt = _random((nc[0], nc[1], H, W), 100 * H + W)
+    loss, l1, ssim, grad = _fused(img, gt)
+    ref = O.image_loss(img, gt, LAM)
+    _close_scalar(loss, ref["loss"], "loss")
+    _close_scalar(l1, ref["l1"], "l1")
+    _close_scalar(ssim, ref["ssim"], "ssim")
+    _grad_bar(grad, ref["grad_loss"], "grad_loss", floor=1.0 / img.numel())
+
+
+def test_unaligned_planes_take_the_element_path():
+    """W % 4 == 0 but an image and a ground truth whose planes start 4 bytes off a 16-byte boundary: the same bits as the
+    aligned call, which stages with float4 loads."""
+    from image_loss import fused_l1_dssim
+    img, gt = _random((2, 3, 20, 68), 18)
+    want = _fused(img, gt)
+
+    def shifted(t):
+        flat = torch.empty(t.numel() + 1, device=DEV)
+        flat[1:] = t.reshape(-1)
+        s = flat[1:].view(t.shape)
+        assert s.data_ptr() % 16 == 4 and s.is_contiguous()
+        return s
+    x = shifted(img).requires_grad_(True)
+    loss, l1, ssim = fused_l1_dssim(x, shifted(gt), LAM, return_parts=True)
+    loss.backward()
+    assert x.data_ptr() % 16 == 4
+    for got, w, what in zip((loss.detach(), l1, ssim, x.grad), want, ("loss", "l1", "ssim", "grad")):
+        assert torch.equal(got, w), what
+
+
 def test_upstream_gradient_scales_the_result():
     img, gt = _random((3, 96, 80), 12)
     _l, _a, _b, g1 = _fused(img, gt)
