@@ -385,7 +385,7 @@ CountReadback* count_readback(hipStream_t s, bool may_create) {
 
 extern "C" {
 
-int f3dgs_version(void) { return 31100; }   // 3.11.0 (major * 10000 + minor * 100 + patch): 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
+int f3dgs_version(void) { return 31200; }   // 3.12.0 (major * 10000 + minor * 100 + patch): 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
 
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 
@@ -794,6 +794,42 @@ int f3dgs_backward(int P, int D, int M, int C, int R, const float* background, i
     if ((rc = check_debug(debug, s, "preprocess backward"))) return rc;
     tm.mark("preprocess_bwd");
     HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+int f3dgs_contributions(int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
+                        const char* image_buffer, int K, const float* masks, float* acc, float* wmax, float* alpha,
+                        float* median_depth, int* ids, float* id_weight, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: P < 0");
+    if (R < 0 || width <= 0 || height <= 0)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: bad sizes (R = %d, image %d x %d)", R, width, height);
+    if (K < 0 || K > F3DGS_CONTRIB_MAX_MASKS)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d masks, 0 .. %d are taken per call", K, F3DGS_CONTRIB_MAX_MASKS);
+    if (K > 0 && !masks) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d but masks is null", K);
+    if (K > 0 && !acc) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d masks but acc is null", K);
+    if (P > 0 && (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)))
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: null state buffer");
+    if (!acc && !wmax && !alpha && !median_depth && !ids && !id_weight)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: every output is null");
+    if (P == 0) {      // no forward state: nothing blended anywhere; the per-Gaussian outputs have no rows
+        if (!alpha && !median_depth && !ids && !id_weight) return F3DGS_OK;
+        HIP_TRY(launch_contributions(width, height, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, alpha,
+                                     median_depth, ids, id_weight, s));
+        return F3DGS_OK;
+    }
+    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
+    const size_t HW = (size_t)width * height, tiles = (size_t)gx * gy;
+    const GeomState geom = GeomState::carve(const_cast<char*>(geom_buffer), P, nullptr);
+    const ImageState img = ImageState::carve(const_cast<char*>(image_buffer), HW, tiles, nullptr);
+    // the sorted list sits at offset 0 of the binning buffer whatever length it was carved for (BinState::list_of); with R = 0
+    // every range is empty and it is never read
+    const uint32_t* point_list = binning_buffer ? BinState::list_of(binning_buffer) : nullptr;
+    float long_axis = 0.f;
+    int b0 = 0, b1 = gy;      // the tile rows the forward call listed (a note that is gone: the whole grid - right, only unbalanced)
+    if (frame_axis_ratio(geom_buffer, &long_axis, &b0, &b1)) { b0 = std::min(std::max(b0, 0), gy); b1 = std::min(std::max(b1, b0), gy); }
+    HIP_TRY(launch_contributions(width, height, b0, b1, img.ranges, point_list, geom.rec, img.n_contrib, K, masks, acc, wmax, alpha,
+                                 median_depth, ids, id_weight, s));
     return F3DGS_OK;
 }
 

@@ -520,6 +520,64 @@ EditSelect(torch::Tensor& features, const torch::Tensor& text, uint64_t positive
     return std::make_tuple(mask, score, op_out);
 }
 
+// the contribution pass (include/f3dgs.h: f3dgs_contributions) over the state buffers of a rasterize_gaussians call: masks
+// (K, H, W) float32 or None; acc (P, K + 1) float32, added to, or None; wmax (P) float32, max-ed into, or None; want_pixel: the
+// four per-pixel outputs.  Returns (alpha, median_depth, ids, id_weight), each (H, W), or four None.
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+Contributions(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imgBuffer, int64_t P,
+              int64_t num_rendered, int64_t H, int64_t W, const c10::optional<torch::Tensor>& masks, c10::optional<torch::Tensor> acc,
+              c10::optional<torch::Tensor> wmax, bool want_pixel) {
+    TORCH_CHECK(imgBuffer.is_cuda() && geomBuffer.is_cuda() && binningBuffer.is_cuda(),
+                "contributions: the state buffers must live on a HIP device (no CPU path)");
+    TORCH_CHECK(P >= 0 && H > 0 && W > 0 && H * W < (1ll << 31), "contributions: bad sizes P = ", P, ", image ", H, " x ", W);
+    const auto dev = imgBuffer.device();
+    auto on_dev_f32 = [&](const torch::Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.device() == dev, "contributions: ", name, " must live on the HIP device of the state buffers (got ",
+                    t.device(), ")");
+        TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous(), "contributions: ", name, " must be contiguous float32");
+    };
+    int64_t K = 0;
+    if (masks.has_value()) {
+        on_dev_f32(*masks, "masks");
+        TORCH_CHECK(masks->dim() == 3 && masks->size(1) == H && masks->size(2) == W, "contributions: masks (K, ", H, ", ", W,
+                    ") expected, got ", masks->sizes());
+        K = masks->size(0);
+        TORCH_CHECK(K <= F3DGS_CONTRIB_MAX_MASKS, "contributions: ", K, " masks, at most ", F3DGS_CONTRIB_MAX_MASKS, " per call");
+        TORCH_CHECK(K == 0 || acc.has_value(), "contributions: masks without acc");
+    }
+    if (acc.has_value()) {
+        on_dev_f32(*acc, "acc");
+        TORCH_CHECK(acc->dim() == 2 && acc->size(0) == P && acc->size(1) == K + 1, "contributions: acc (", P, ", ", K + 1,
+                    ") expected, got ", acc->sizes());
+    }
+    if (wmax.has_value()) {
+        on_dev_f32(*wmax, "wmax");
+        TORCH_CHECK(wmax->dim() == 1 && wmax->size(0) == P, "contributions: wmax (", P, ") expected, got ", wmax->sizes());
+    }
+    TORCH_CHECK(acc.has_value() || wmax.has_value() || want_pixel, "contributions: no output asked for");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    c10::optional<torch::Tensor> alpha, median, ids, id_weight;
+    if (want_pixel) {
+        auto f32 = imgBuffer.options().dtype(torch::kFloat32);
+        alpha = torch::empty({H, W}, f32);
+        median = torch::empty({H, W}, f32);
+        ids = torch::empty({H, W}, imgBuffer.options().dtype(torch::kInt32));
+        id_weight = torch::empty({H, W}, f32);
+    }
+    auto state = [](const torch::Tensor& t) { return t.numel() ? reinterpret_cast<const char*>(t.data_ptr()) : nullptr; };
+    const bool per_gaussian = P > 0;      // (P, .) tensors of no rows have no storage: nothing to add to
+    if (!per_gaussian) K = 0;
+    if (!per_gaussian && !want_pixel) return std::make_tuple(alpha, median, ids, id_weight);
+    const int rc = f3dgs_contributions(
+        (int)P, (int)num_rendered, (int)W, (int)H, state(geomBuffer), state(binningBuffer), state(imgBuffer), (int)K,
+        K ? masks->data_ptr<float>() : nullptr, (acc.has_value() && per_gaussian) ? acc->data_ptr<float>() : nullptr,
+        (wmax.has_value() && per_gaussian) ? wmax->data_ptr<float>() : nullptr, want_pixel ? alpha->data_ptr<float>() : nullptr,
+        want_pixel ? median->data_ptr<float>() : nullptr, want_pixel ? ids->data_ptr<int>() : nullptr,
+        want_pixel ? id_weight->data_ptr<float>() : nullptr, current_stream(imgBuffer));
+    check_status(rc, "contributions");
+    return std::make_tuple(alpha, median, ids, id_weight);
+}
+
 // open-vocabulary segmentation (include/f3dgs.h: f3dgs_segment).  feature_map (C,H,W), text (K,Cout) float32; weight (Cout,C) /
 // bias (Cout) or empty tensors.  Returns (labels (Hs,Ws) int64, score (Hs,Ws) float32 or None).
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>>
@@ -850,6 +908,10 @@ PYBIND11_MODULE(_C, m) {
           py::arg("opacity") = py::none());
     m.def("segment", &Segment, py::arg("feature_map"), py::arg("text"), py::arg("Hs"), py::arg("Ws"), py::arg("weight"), py::arg("bias"),
           py::arg("flags"), py::arg("want_score"));
+    m.def("contributions", &Contributions, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imgBuffer"), py::arg("P"),
+          py::arg("num_rendered"), py::arg("H"), py::arg("W"), py::arg("masks") = py::none(), py::arg("acc") = py::none(),
+          py::arg("wmax") = py::none(), py::arg("want_pixel") = true);
+    m.attr("CONTRIB_MAX_MASKS") = (int)F3DGS_CONTRIB_MAX_MASKS;
     m.def("feature_pca_moments", &FeaturePcaMoments, py::arg("feature_map"), py::arg("stride"));
     m.def("feature_pca_project", &FeaturePcaProject, py::arg("feature_map"), py::arg("mean"), py::arg("components"),
           py::arg("lo") = py::none(), py::arg("hi") = py::none());

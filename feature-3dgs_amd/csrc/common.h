@@ -360,6 +360,11 @@ int launch_render_backward(const ViewParams& vp, int C, const uint2* ranges, con
                            const float* dL_dpix, const float* dL_dfeat, const float* dL_ddepth, float* grec,
                            float* dL_dfeature, const uint32_t* tile_len, uint32_t* tile_order, const LowresGrad* lowres,
                            int contraction, const uint32_t* gate, hipStream_t s);      // (vp.band0 / band1: the forward call's band, see band_perm)
+// contrib.hip: the contribution pass over a finished forward call's lists (f3dgs_contributions).  `ranges` null: no forward
+// state (P == 0), every tile empty.  band0 / band1: the forward call's band (workgroup order only, see band_perm).
+hipError_t launch_contributions(int W, int H, int band0, int band1, const uint2* ranges, const uint32_t* point_list, const SplatRec* rec,
+                                const uint32_t* n_contrib, int K, const float* masks, float* acc, float* wmax, float* alpha,
+                                float* median_depth, int* ids, float* id_weight, hipStream_t s);
 struct BwdArgs;
 void launch_render_backward_pl(BwdArgs a, int C, hipStream_t s);     // render_bwd_pl.hip
 void launch_tile_order(const uint32_t* tile_len, size_t tiles, uint32_t* order, uint32_t band_b0, uint32_t band_tb, hipStream_t s);

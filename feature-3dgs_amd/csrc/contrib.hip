@@ -1,0 +1,254 @@
+// contrib.hip — the contribution pass: one more walk over the tile lists of a finished forward call that answers "which
+// Gaussians lie behind this region of the view?" (include/f3dgs.h: f3dgs_contributions).  No counterpart in the reference,
+// whose only route from a 2D mask to the Gaussians is the blend backward with the masks as upstream gradient.
+//
+// Per (pixel, list entry) the blend weight w = alpha T is formed with the forward's own instruction sequence (render_common.h:
+// splat_power2 on the conic scaled at staging, v_exp_f32, the 0.99 clamp, the power > 0 and alpha < 1/255 skips, T *= 1 - alpha)
+// and the set of contributors is the forward's n_contrib - the T < 1e-4 termination is not decided a second time - so the
+// weights are the forward's, bit for bit.  From them:
+//   per pixel     alpha = 1 - T_final, the depth at which T crosses 0.5 (Q4: no background, 0 when it never does), the index
+//                 and the weight of the entry of largest weight (strict >: the earliest of a tie);
+//   per Gaussian  acc[g][k] += sum over pixels of w masks[k][pixel] (k < K), acc[g][K] += sum of w, wmax[g] = max(wmax[g], w).
+//
+// Decomposition of render_common.h: one 16x16 tile per workgroup, a wave per 8x8 quadrant, chunks of 64 list entries staged in
+// the wave's LDS slice behind the forward's record / list prefetch pipeline and its wave-level footprint test (rect_hit: an
+// entry it drops cannot reach 1/255 at any pixel of the quadrant, so it would be skipped sixty-four times anyway).
+//
+// The per-Gaussian sums leave the wave through registers only (no LDS atomics: DESIGN 8): the up to eight columns a lane
+// carries are reduce-scattered over the wave - at each of the first log2(columns) lane-exchange steps a lane keeps half of its
+// columns and hands the other half to its partner, then the one column left is summed over the remaining steps: 7 + 3 adds for
+// eight columns instead of 6 x 8 - and the lanes 0 .. columns - 1 issue ONE global atomic for the wave and the entry, one dword
+// each on consecutive addresses.  Nothing is issued for an entry no lane blends, nor for a column whose sum is zero.
+#include "render_common.h"
+
+namespace f3dgs {
+
+namespace {
+
+struct ContribArgs {
+    const uint2* ranges;          // null: no forward state (P == 0) - every tile is empty
+    const uint32_t* point_list;
+    const SplatRec* rec;
+    const uint32_t* n_contrib;
+    const float* masks;           // K x H x W
+    float* acc;                   // P x (K + 1), added to
+    float* wmax;                  // P, max-ed into (non-negative floats: their bit patterns order like unsigned integers)
+    float* alpha;                 // H x W each
+    float* median_depth;
+    int* ids;
+    float* id_weight;
+    int W, H, gx, gy, K;
+    uint32_t band_b0, band_tb;    // band_perm (common.h): the forward call's band, (0, 0) = whole view
+};
+
+struct ContribChunk {
+    float4 geo[64];    // mean_x, mean_y, conic_a', conic_b' (scaled, see splat_power2)
+    float4 tail[64];   // conic_c', opacity, depth, Gaussian index (bits)
+    uint32_t pos[64];  // 1-based list position
+};
+
+// value of lane (l ^ (1 << STEP)), all 64 lanes taking part
+template <int STEP>
+__device__ __forceinline__ float lane_xor(float v) {
+    if constexpr (STEP == 0) return dpp_get<0xB1>(v);                     // quad_perm [1,0,3,2]
+    else if constexpr (STEP == 1) return dpp_get<0x4E>(v);                // quad_perm [2,3,0,1]
+    else if constexpr (STEP == 2) return dpp_get<0x1B>(dpp_get<0x141>(v));   // row_half_mirror (l ^ 7), then quad_perm [3,2,1,0] (l ^ 3)
+    else if constexpr (STEP == 3) return dpp_get<0x128>(v);               // row_ror:8
+    else {
+        // v_permlane16_swap / v_permlane32_swap of a register with itself: one result holds the even rows (the low half)
+        // twice, the other the odd rows (the high half) twice - whichever of the two is not the lane's own is its partner's
+        const int x = __float_as_int(v);
+        if constexpr (STEP == 4) {
+            const auto sw = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+            return __int_as_float(sw[0] ^ sw[1] ^ x);
+        } else {
+            const auto sw = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+            return __int_as_float(sw[0] ^ sw[1] ^ x);
+        }
+    }
+}
+
+// Sums v[c] over the 64 lanes for NC columns at once.  Returns, in EVERY lane, the wave's total of column contrib_column(lane).
+template <int NC, int STEP = 0>
+__device__ __forceinline__ float reduce_scatter(float (&v)[NC], int lane) {
+    if constexpr (NC == 1) {
+        float s = v[0];
+        if constexpr (STEP <= 0) s += lane_xor<0>(s);
+        if constexpr (STEP <= 1) s += lane_xor<1>(s);
+        if constexpr (STEP <= 2) s += lane_xor<2>(s);
+        s += lane_xor<3>(s);
+        s += lane_xor<4>(s);
+        s += lane_xor<5>(s);
+        return s;
+    } else {
+        constexpr int HALF = NC / 2;
+        const bool hi = (lane >> STEP) & 1;
+        float k[HALF];
+#pragma unroll
+        for (int i = 0; i < HALF; i++) {
+            const float keep = hi ? v[i + HALF] : v[i];
+            const float send = hi ? v[i] : v[i + HALF];
+            k[i] = keep + lane_xor<STEP>(send);
+        }
+        return reduce_scatter<HALF, STEP + 1>(k, lane);
+    }
+}
+// the column reduce_scatter<NC> leaves in a lane: the low log2(NC) lane bits, reversed
+template <int NC>
+__device__ __forceinline__ int contrib_column(int lane) {
+    int c = 0;
+#pragma unroll
+    for (int b = 0; (1 << b) < NC; b++) c = 2 * c + ((lane >> b) & 1);
+    return c;
+}
+__device__ __forceinline__ uint32_t wave_max_bits(float w) {
+    // weights are >= 0: the float order is the order of the bit patterns
+    float m = w;
+    m = fmaxf(m, lane_xor<0>(m));
+    m = fmaxf(m, lane_xor<1>(m));
+    m = fmaxf(m, lane_xor<2>(m));
+    m = fmaxf(m, lane_xor<3>(m));
+    m = fmaxf(m, lane_xor<4>(m));
+    m = fmaxf(m, lane_xor<5>(m));
+    return __float_as_uint(m);
+}
+
+// NC: columns of `acc` carried, K + 1 rounded up to a power of two (0: no per-Gaussian sums); PIX: the per-pixel outputs
+template <int NC, bool PIX>
+__global__ void __launch_bounds__(256) contrib_kernel(ContribArgs a) {
+    constexpr int NV = NC > 0 ? NC : 1;
+    __shared__ __attribute__((aligned(16))) ContribChunk chunks[4];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    ContribChunk& ck = chunks[wave];
+
+    const uint32_t vb = xcd_remap(blockIdx.x, gridDim.x);
+    const uint32_t tile = band_perm(vb, (uint32_t)(a.gx * a.gy), a.band_b0, a.band_tb);
+    const int tx = tile % a.gx, ty = tile / a.gx;
+    const uint2 rg = a.ranges ? a.ranges[tile] : make_uint2(0u, 0u);
+    const uint32_t r_lo = __builtin_amdgcn_readfirstlane((int)rg.x);
+    uint32_t r_hi = __builtin_amdgcn_readfirstlane((int)rg.y);
+
+    // pixel-centre rectangle of this wave's quadrant, for the wave-level footprint test (scalar integers, see sgpr_opaque)
+    const int iwx0 = tx * TILE + (wave & 1) * 8, iwy0 = ty * TILE + (wave >> 1) * 8;
+    const int x = iwx0 + (lane & 7), y = iwy0 + (lane >> 3);
+    const bool inside = x < a.W && y < a.H;
+    const size_t pid = (size_t)y * a.W + x;
+    const float pxf = (float)x, pyf = (float)y;
+    // the forward's own contributors: list positions up to n_contrib (an entry behind it never blended, see render_fwd.hip)
+    const uint32_t last = (inside && r_lo < r_hi) ? a.n_contrib[pid] : 0u;
+    r_hi = min(r_hi, r_lo + (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(last)));
+
+    float mv[NV];      // the pixel's mask values; column K carries the weight itself, the padding columns nothing
+    if constexpr (NC > 0) {
+        const size_t HW = (size_t)a.W * a.H;
+#pragma unroll
+        for (int c = 0; c < NC; c++) mv[c] = c < a.K ? (inside ? a.masks[(size_t)c * HW + pid] : 0.0f) : (c == a.K ? 1.0f : 0.0f);
+    }
+
+    float T = 1.0f, med = 0.0f, best_w = 0.0f;
+    int best = -1;
+
+    // software pipeline of the blend forward: the splat records of chunk k+1 and the list ids of chunk k+2 are requested while
+    // chunk k is walked
+    uint32_t n_id = 0, f_id = 0;
+    float4 n_q0 = make_float4(0, 0, 0, 0), n_q1 = n_q0;
+    float n_depth = 0.f;
+    if (r_lo + lane < r_hi) n_id = a.point_list[r_lo + lane];
+    if (r_lo + 64 + lane < r_hi) f_id = a.point_list[r_lo + 64 + lane];
+    if (r_lo + lane < r_hi) {
+        const SplatRec* rp = a.rec + n_id;
+        n_q0 = rp->q0; n_q1 = rp->q1; n_depth = rp->q2.y;
+    }
+    for (uint32_t base = r_lo; base < r_hi; base += 64) {
+        const int cnt_in = (int)min(64u, r_hi - base);
+        const bool hit = lane < cnt_in && rect_hit(n_q0.x, n_q0.y, n_q0.z, n_q0.w, n_q1.x, n_q1.y, (float)sgpr_opaque(iwx0),
+                                                   (float)sgpr_opaque(iwx0 + 7), (float)sgpr_opaque(iwy0), (float)sgpr_opaque(iwy0 + 7));
+        const unsigned long long hmask = __ballot(hit);
+        const int cnt = __popcll(hmask);
+        const int slot = __popcll(hmask & ((1ull << lane) - 1ull));
+        __builtin_amdgcn_wave_barrier();
+        if (hit) {
+            ck.geo[slot] = make_float4(n_q0.x, n_q0.y, n_q0.z * CONIC_SCALE_AC, n_q0.w * CONIC_SCALE_B);   // see splat_power2
+            ck.tail[slot] = make_float4(n_q1.x * CONIC_SCALE_AC, n_q1.y, n_depth, __uint_as_float(n_id));
+            ck.pos[slot] = base - r_lo + lane + 1;
+        }
+        __builtin_amdgcn_wave_barrier();
+        n_id = f_id;
+        if (base + 64 + lane < r_hi) {
+            const SplatRec* rp = a.rec + n_id;
+            n_q0 = rp->q0; n_q1 = rp->q1; n_depth = rp->q2.y;
+        }
+        if (base + 128 + lane < r_hi) f_id = a.point_list[base + 128 + lane];
+
+        for (int j = 0; j < cnt; j++) {
+            const float4 g0 = ck.geo[j];
+            const float4 g1 = ck.tail[j];
+            const uint32_t pos = ck.pos[j];
+            const float dx = g0.x - pxf, dy = g0.y - pyf;
+            const float power = splat_power2(dx, dy, g0.z, g0.w, g1.x);
+            const float alpha = fminf(ALPHA_MAX, g1.y * __builtin_amdgcn_exp2f(power));
+            const bool ok = !(power > 0.0f) && !(alpha < ALPHA_MIN) && pos <= last;
+            if (!__any(ok)) continue;
+            const float w = ok ? alpha * T : 0.0f;
+            const float Tn = ok ? T * (1.0f - alpha) : T;
+            const uint32_t g = __builtin_amdgcn_readfirstlane((int)__float_as_uint(g1.w));
+            if constexpr (PIX) {
+                med = (T >= 0.5f && Tn < 0.5f) ? g1.z : med;     // T only moves at a blended entry, and crosses 0.5 once
+                const bool better = w > best_w;
+                best = better ? (int)g : best;
+                best_w = better ? w : best_w;
+            }
+            T = Tn;
+            if constexpr (NC > 0) {
+                float v[NC];
+#pragma unroll
+                for (int c = 0; c < NC; c++) v[c] = w * mv[c];
+                const float s = reduce_scatter<NC>(v, lane);
+                const int col = contrib_column<NC>(lane);
+                if (lane < NC && col <= a.K && s != 0.0f) unsafeAtomicAdd(a.acc + (size_t)g * (a.K + 1) + col, s);
+            }
+            if (a.wmax) {
+                const uint32_t m = wave_max_bits(w);
+                if (lane == 0) atomicMax(reinterpret_cast<uint32_t*>(a.wmax) + g, m);
+            }
+        }
+    }
+
+    if constexpr (PIX) {
+        if (inside) {
+            if (a.alpha) a.alpha[pid] = 1.0f - T;
+            if (a.median_depth) a.median_depth[pid] = med;
+            if (a.ids) a.ids[pid] = best;
+            if (a.id_weight) a.id_weight[pid] = best_w;
+        }
+    }
+}
+
+template <bool PIX>
+void launch_by_columns(const ContribArgs& a, bool sums, hipStream_t s) {
+    const dim3 grid(a.gx * a.gy), block(256);
+    if (!sums) hipLaunchKernelGGL((contrib_kernel<0, PIX>), grid, block, 0, s, a);
+    else if (a.K + 1 <= 1) hipLaunchKernelGGL((contrib_kernel<1, PIX>), grid, block, 0, s, a);
+    else if (a.K + 1 <= 2) hipLaunchKernelGGL((contrib_kernel<2, PIX>), grid, block, 0, s, a);
+    else if (a.K + 1 <= 4) hipLaunchKernelGGL((contrib_kernel<4, PIX>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((contrib_kernel<8, PIX>), grid, block, 0, s, a);
+}
+
+}  // namespace
+
+hipError_t launch_contributions(int W, int H, int band0, int band1, const uint2* ranges, const uint32_t* point_list, const SplatRec* rec,
+                                const uint32_t* n_contrib, int K, const float* masks, float* acc, float* wmax, float* alpha,
+                                float* median_depth, int* ids, float* id_weight, hipStream_t s) {
+    ContribArgs a;
+    a.ranges = ranges; a.point_list = point_list; a.rec = rec; a.n_contrib = n_contrib;
+    a.masks = masks; a.acc = acc; a.wmax = wmax;
+    a.alpha = alpha; a.median_depth = median_depth; a.ids = ids; a.id_weight = id_weight;
+    a.W = W; a.H = H; a.gx = (W + TILE - 1) / TILE; a.gy = (H + TILE - 1) / TILE; a.K = K;
+    band_perm_params(a.gx, a.gy, band0, band1, &a.band_b0, &a.band_tb);
+    const bool pix = alpha || median_depth || ids || id_weight;
+    if (pix) launch_by_columns<true>(a, acc != nullptr, s); else launch_by_columns<false>(a, acc != nullptr, s);
+    return hipGetLastError();
+}
+
+}  // namespace f3dgs

@@ -440,6 +440,39 @@ int f3dgs_edit_select(int P, int C, int K, const float* features, float* normali
                       void* stream /* hipStream_t */);
 
 /*
+ * The contribution pass (no counterpart in the reference, whose only route from a region of a rendered view back to the
+ * Gaussians behind it is a backward call with the region as upstream gradient): one more walk over the tile lists of a finished
+ * f3dgs_forward call, found in its three state buffers as f3dgs_backward finds them (P, R = num_rendered, width and height of
+ * that call; a call made under f3dgs_set_tile_band needs nothing more: tiles outside the band have empty lists).  For pixel p
+ * and list position k <= n_contrib[p] the weight is w = alpha * T, formed with the forward's own instruction sequence and the
+ * forward's own set of contributors: the pass reproduces the forward's blend weights bit for bit.  Every output is optional,
+ * NULL = not wanted, and the work for it is then skipped; at least one must be given.
+ *   Per pixel, H x W each, fully written (empty tiles, P == 0 and R == 0 included):
+ *     alpha         float   1 - T_final
+ *     median_depth  float   the view-space depth of the first blended entry after which T < 0.5; 0 where T never gets there
+ *                           (no background on depth, as for the depth image)
+ *     ids           int32   the Gaussian of the blended entry of largest weight - the earliest one of an exact tie -, -1 where
+ *                           nothing blended
+ *     id_weight     float   that entry's weight, or 0
+ *   Per Gaussian:
+ *     acc           (P, K + 1) floats, ADDED TO (the caller zeroes it once and may accumulate many views): column k < K receives
+ *                   the sum over the pixels of w * masks[k][pixel], column K the sum of w.  masks: (K, H, W) floats, any values
+ *                   (soft masks), 0 <= K <= F3DGS_CONTRIB_MAX_MASKS; the products are plain fp32.  K = 0: the weight total alone.
+ *     wmax          (P) floats, MAX-ED INTO: the largest weight the Gaussian reaches at any pixel.  Weights are >= 0 and the
+ *                   maximum is taken on the bit patterns: the buffer must hold non-negative values (zeros to begin with).
+ * The sums of `acc` arrive through float atomics in a varying order: like the gradients of f3dgs_backward they are not
+ * bit-reproducible between runs.  wmax and every per-pixel output are.  F3DGS_ERR_INVALID_ARGUMENT, before any device work:
+ * P < 0, a bad size, K out of range, K > 0 without masks or without acc, a null state buffer while P > 0 (binning_buffer may
+ * be NULL when R == 0), every output NULL.  No scratch, no host read, no memset; one launch on `stream`: capturable.
+ */
+#define F3DGS_CONTRIB_MAX_MASKS 7
+int f3dgs_contributions(int P, int R, int width, int height,
+                        const char* geom_buffer, const char* binning_buffer, const char* image_buffer,
+                        int K, const float* masks /* K x H x W */, float* acc /* P x (K + 1) */, float* wmax /* P */,
+                        float* alpha, float* median_depth, int* ids, float* id_weight /* H x W each */,
+                        void* stream /* hipStream_t */);
+
+/*
  * Forward-only counterpart (the inference side, render.py:169-171, :137-139, :294-296): the rendered feature map (C,H,W)
  * is resized (bilinear, align_corners=True) to (Hg,Wg) and - if weight / bias are given - decoded by the 1x1 conv into
  * `out` (Cout,Hg,Wg), fp32 or (out_is_half != 0) IEEE fp16 as render.py stores it.  Without a decoder Cout must equal C.
