@@ -476,6 +476,92 @@ ImageMetrics(const torch::Tensor& image, const torch::Tensor& gt, int64_t image_
     return std::make_tuple(l1, mse, psnr, ssim);
 }
 
+// segmentation scores of N view pairs (include/f3dgs.h: f3dgs_seg_metrics).  teacher, student, gt (empty: none): (N,H,W) uint8,
+// int32 or int64, each by itself; a view at an odd storage offset is read where it lies.  carry_counts (A,L) / carry_scalars (5):
+// the pooled counters of an earlier call, or empty.  Returns (counts (A,N+1,L) int64, scalars (5,N+1) int64, scores (2K,N+1)
+// float64, iou_per_label (K,N+1,L) float64, labels_ranked (K,N+1,num_classes) int64); row N is the pooled one.  want_scores = false:
+// the last three are empty and the finish kernel only pools the counters.
+static int label_format(const torch::Tensor& t, const char* where, const char* name) {
+    TORCH_CHECK(t.is_cuda(), where, ": ", name, " must live on a HIP device (no CPU path)");
+    TORCH_CHECK(t.dim() == 3, where, ": ", name, " must be (N,H,W), got ", t.dim(), " dimensions");
+    for (int i = 0; i < 3; i++) TORCH_CHECK(t.size(i) < (1ll << 31), where, ": ", name, " is too large");
+    switch (t.scalar_type()) {
+        case torch::kByte: return F3DGS_LABELS_U8;
+        case torch::kInt32: return F3DGS_LABELS_I32;
+        case torch::kInt64: return F3DGS_LABELS_I64;
+        default: TORCH_CHECK(false, where, ": ", name, " must be uint8, int32 or int64, got ", t.scalar_type());
+    }
+    return -1;
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+SegMetrics(const torch::Tensor& teacher, const torch::Tensor& student, const torch::Tensor& gt, int64_t L, int64_t num_classes,
+           const torch::Tensor& carry_counts, const torch::Tensor& carry_scalars, bool want_scores) {
+    const bool has_gt = gt.numel() != 0 || gt.dim() == 3;
+    const int ft = label_format(teacher, "seg_metrics", "teacher"), fs = label_format(student, "seg_metrics", "student");
+    const int fg = has_gt ? label_format(gt, "seg_metrics", "gt") : F3DGS_LABELS_U8;
+    TORCH_CHECK(teacher.sizes() == student.sizes() && (!has_gt || gt.sizes() == teacher.sizes()), "seg_metrics: label map shapes differ");
+    TORCH_CHECK(teacher.device() == student.device() && (!has_gt || gt.device() == teacher.device()),
+                "seg_metrics: label maps are on different devices");
+    TORCH_CHECK(L >= 1 && L <= F3DGS_SEGMENT_MAX_TEXTS, "seg_metrics: ", L, " label slots: 1 to ", F3DGS_SEGMENT_MAX_TEXTS, " are supported");
+    TORCH_CHECK(num_classes >= 1 && num_classes <= L, "seg_metrics: num_classes ", num_classes, " outside 1..", L);
+    const int64_t N = teacher.size(0), A = has_gt ? 7 : 3, K = has_gt ? 2 : 1;
+    TORCH_CHECK(N >= 1 && teacher.size(1) >= 1 && teacher.size(2) >= 1, "seg_metrics: empty label maps ", teacher.sizes());
+    const bool carry = carry_counts.numel() != 0;
+    if (carry)
+        TORCH_CHECK(carry_counts.is_cuda() && carry_scalars.is_cuda() && carry_counts.scalar_type() == torch::kInt64 &&
+                        carry_scalars.scalar_type() == torch::kInt64 && carry_counts.numel() == A * L && carry_scalars.numel() == 5,
+                    "seg_metrics: carry_counts (", A, ",", L, ") and carry_scalars (5) int64 device tensors expected");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(teacher.device());
+    const torch::Tensor t = teacher.contiguous(), s = student.contiguous(), g = has_gt ? gt.contiguous() : gt;
+    const torch::Tensor cc = carry ? carry_counts.contiguous() : carry_counts, cs = carry ? carry_scalars.contiguous() : carry_scalars;
+    auto oi = t.options().dtype(torch::kInt64), od = t.options().dtype(torch::kFloat64);
+    const int64_t count_words = A * (N + 1) * L;
+    torch::Tensor block = torch::empty({(long long)(f3dgs_seg_metrics_scratch_bytes((int)N, (int)L, has_gt) / sizeof(int64_t))}, oi);
+    TORCH_CHECK(block.numel() == count_words + 5 * (N + 1), "seg_metrics: unexpected counter block size");
+    // without want_scores the three are empty and the library gets NULL: the counters alone (row N still pooled)
+    const int64_t S = want_scores ? 1 : 0;
+    torch::Tensor scores = torch::empty({S * 2 * K, N + 1}, od), per_label = torch::empty({S * K, N + 1, L}, od);
+    torch::Tensor ranked = torch::empty({S * K, N + 1, num_classes}, oi);
+    const int rc = f3dgs_seg_metrics((int)N, (int)t.size(1), (int)t.size(2), (int)L, (int)num_classes, t.data_ptr(), ft, s.data_ptr(), fs,
+                                     has_gt ? g.data_ptr() : nullptr, fg, carry ? cc.data_ptr<int64_t>() : nullptr,
+                                     carry ? cs.data_ptr<int64_t>() : nullptr, block.data_ptr<int64_t>(),
+                                     want_scores ? scores.data_ptr<double>() : nullptr, want_scores ? per_label.data_ptr<double>() : nullptr,
+                                     want_scores ? ranked.data_ptr<int64_t>() : nullptr, current_stream(t));
+    check_status(rc, "seg_metrics");
+    return std::make_tuple(block.narrow(0, 0, count_words).view({A, N + 1, L}), block.narrow(0, count_words, 5 * (N + 1)).view({5, N + 1}),
+                           scores, per_label, ranked);
+}
+
+// palette pictures of label maps (include/f3dgs.h: f3dgs_seg_colorize).  labels (N,H,W) uint8 / int32 / int64, palette (L,3) uint8,
+// image (N,3,H,W) float32 or empty (mask mode), fill: three byte values.  Returns uint8 (N,H,W',3), W' = 3 W for the strip.
+torch::Tensor SegColorize(const torch::Tensor& labels, const torch::Tensor& palette, const torch::Tensor& image, int64_t mode, double a,
+                          double b, const std::array<int, 3>& fill) {
+    const int fl = label_format(labels, "seg_colorize", "labels");
+    TORCH_CHECK(palette.is_cuda() && palette.device() == labels.device(), "seg_colorize: palette must live on the labels' device");
+    TORCH_CHECK(palette.scalar_type() == torch::kByte && palette.dim() == 2 && palette.size(1) == 3 && palette.size(0) >= 1 &&
+                    palette.size(0) <= F3DGS_SEGMENT_MAX_TEXTS,
+                "seg_colorize: palette must be (L,3) uint8 with 1 <= L <= ", F3DGS_SEGMENT_MAX_TEXTS, ", got ", palette.sizes());
+    TORCH_CHECK(mode == F3DGS_SEG_COLOR_MASK || mode == F3DGS_SEG_COLOR_BLEND || mode == F3DGS_SEG_COLOR_STRIP, "seg_colorize: unknown mode ", mode);
+    const int64_t N = labels.size(0), H = labels.size(1), W = labels.size(2);
+    TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "seg_colorize: empty label maps ", labels.sizes());
+    const bool need_image = mode != F3DGS_SEG_COLOR_MASK;
+    if (need_image)
+        TORCH_CHECK(image.is_cuda() && image.device() == labels.device() && image.scalar_type() == torch::kFloat32 && image.dim() == 4 &&
+                        image.size(0) == N && image.size(1) == 3 && image.size(2) == H && image.size(3) == W,
+                    "seg_colorize: image must be float32 (", N, ",3,", H, ",", W, ") on the labels' device, got ", image.sizes());
+    for (int v : fill) TORCH_CHECK(v >= 0 && v <= 255, "seg_colorize: fill must be three byte values");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(labels.device());
+    const torch::Tensor l = labels.contiguous(), p = palette.contiguous(), im = need_image ? image.contiguous() : image;
+    torch::Tensor out = torch::empty({N, H, mode == F3DGS_SEG_COLOR_STRIP ? 3 * W : W, 3}, l.options().dtype(torch::kByte));
+    const unsigned char f[3] = {(unsigned char)fill[0], (unsigned char)fill[1], (unsigned char)fill[2]};
+    const int rc = f3dgs_seg_colorize((int)N, (int)H, (int)W, (int)p.size(0), l.data_ptr(), fl, p.data_ptr<unsigned char>(),
+                                      need_image ? im.data_ptr<float>() : nullptr, (int)mode, (float)a, (float)b, f,
+                                      out.data_ptr<unsigned char>(), current_stream(l));
+    check_status(rc, "seg_colorize");
+    return out;
+}
+
 // language-guided selection (include/f3dgs.h: f3dgs_edit_select).  features (P, C) float32, contiguous and 16-byte aligned where
 // normalize_inplace asks for the write-back (edit.py copies other views and copies back); text (K, C).  Returns (mask (P),
 // score (P) or None, opacity_out like opacity or None).
@@ -931,6 +1017,16 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SEGMENT_ROUND_HALF") = (int)F3DGS_SEGMENT_ROUND_HALF;
     m.attr("SEGMENT_TEXT_NORMALIZED") = (int)F3DGS_SEGMENT_TEXT_NORMALIZED;
     m.attr("SEGMENT_MAX_TEXTS") = (int)F3DGS_SEGMENT_MAX_TEXTS;
+    m.def("seg_metrics", &SegMetrics, py::arg("teacher"), py::arg("student"), py::arg("gt"), py::arg("num_labels"), py::arg("num_classes"),
+          py::arg("carry_counts"), py::arg("carry_scalars"), py::arg("want_scores"));
+    m.def("seg_colorize", &SegColorize, py::arg("labels"), py::arg("palette"), py::arg("image"), py::arg("mode"), py::arg("a"), py::arg("b"),
+          py::arg("fill"));
+    m.attr("LABELS_U8") = (int)F3DGS_LABELS_U8;
+    m.attr("LABELS_I32") = (int)F3DGS_LABELS_I32;
+    m.attr("LABELS_I64") = (int)F3DGS_LABELS_I64;
+    m.attr("SEG_COLOR_MASK") = (int)F3DGS_SEG_COLOR_MASK;
+    m.attr("SEG_COLOR_BLEND") = (int)F3DGS_SEG_COLOR_BLEND;
+    m.attr("SEG_COLOR_STRIP") = (int)F3DGS_SEG_COLOR_STRIP;
     m.attr("EDIT_SELECT") = (int)F3DGS_EDIT_SELECT;
     m.attr("EDIT_DELETE") = (int)F3DGS_EDIT_DELETE;
     m.attr("EDIT_TEXT_NORMALIZED") = (int)F3DGS_EDIT_TEXT_NORMALIZED;

@@ -112,7 +112,8 @@ def segment_reference_chain(feature_map: torch.Tensor, text_features: torch.Tens
 def label_agreement(teacher: torch.Tensor, student: torch.Tensor, num_classes: int):
     """(accuracy, mean IoU) of two label maps as encoders/lseg_encoder/segmentation_metric.py:58-61, 76-90 compute them:
     the share of equal pixels, and the NaN-mean of intersection / union over the `num_classes` most frequent labels of the
-    concatenation of both maps.  Plain torch on the labels' device; returns two Python floats."""
+    concatenation of both maps.  Plain torch on the labels' device; returns two Python floats.
+    (seg_metrics.py scores whole test sets with HIP kernels and one host read, by the same rule for equal counts.)"""
     if teacher.shape != student.shape:
         raise ValueError(f"label maps of shapes {tuple(teacher.shape)} and {tuple(student.shape)}")
     if teacher.numel() == 0:

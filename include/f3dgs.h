@@ -508,6 +508,68 @@ int f3dgs_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const fl
                   float* score /* Hs*Ws or NULL */, void* scratch, void* stream /* hipStream_t */);
 
 /*
+ * Segmentation scores of N rendered views (the scoring half of the semantic-segmentation evaluation:
+ * encoders/lseg_encoder/segmentation_metric.py:58-108 calculate_accuracy, calculate_accuracy_mask, calculate_iou,
+ * calculate_iou_mask, called per view at :818-832), in one launch chain.  `teacher`, `student` and the optional `gt` (NULL: the
+ * gt-dependent results are not produced) are N x H x W label maps, contiguous, each in its own format F3DGS_LABELS_U8 (what a
+ * label PNG holds), _I32 or _I64 (what f3dgs_segment writes); a base pointer needs the alignment of its element only (a sliced
+ * tensor): whole aligned groups of four elements are read by vector loads, the ends of the block element by element.
+ * L label slots, 1 <= L <= F3DGS_SEGMENT_MAX_TEXTS.  A pixel is VALID when each of its labels in the maps given lies in [0, L) -
+ * compared on the full-width value, before it is narrowed or used as an index; any other pixel counts in `invalid` and in
+ * nothing else.  Over the valid pixels of view n, with match := (gt == teacher), all integers:
+ *   n_t[i], n_s[i], n_g[i]   teacher == i, student == i, gt == i            n_ts[i]   teacher == i and student == i
+ *   m_g[i], m_s[i], m_gs[i]  match and gt == i; match and student == i; match and gt == i and student == i
+ *   valid, equal, invalid, matched, correct   valid pixels; teacher == student; pixels left out; match; match and student == gt
+ * `counters` (f3dgs_seg_metrics_scratch_bytes(N, L, gt != NULL) bytes, uninitialised, 8-byte aligned; it is cleared by a kernel)
+ * holds them after the call: int64 counts[A][N + 1][L] with the arrays in the order n_t, n_s, n_ts (A = 3) and, with gt, n_g,
+ * m_g, m_s, m_gs (A = 7), followed by int64 scalars[5][N + 1] in the order valid, equal, invalid, matched, correct (the last two
+ * stay 0 without gt).  Row N is the POOLED row: the label-wise sums of the counters over the N views, plus - if given - those of
+ * earlier calls, `carry_counts` (A x L) and `carry_scalars` (5), both NULL or both given: a test set of views of several sizes
+ * is pooled by chaining its calls.  Per row, views and the pooled one, in fp64:
+ *   scores[0][row] accuracy = equal / valid            scores[2][row] accuracy_masked = correct / matched      (0 / 0 = NaN, as
+ *   scores[1][row] iou                                 scores[3][row] iou_masked                                the reference)
+ *   iou:        the labels ranked by n_t + n_s, descending, THE LOWER LABEL FIRST AMONG EQUAL COUNTS (the reference's argsort
+ *               leaves that order open); kept are the first `num_classes` whose count is not zero; iou_i = n_ts / (n_t + n_s -
+ *               n_ts); the mean of the kept values that are not NaN, added in rank order, NaN when there is none
+ *   iou_masked: ranked by n_g + n_t + n_s; iou_i = m_gs / (m_g + m_s - m_gs), a union of 0 gives NaN and the label is skipped
+ *               (np.nanmean)
+ * `scores` is [2 K][N + 1], `iou_per_label` [K][N + 1][L] (NaN where the label did not make the cut) and `labels_ranked`
+ * [K][N + 1][num_classes] (the kept labels in rank order, padded with -1), K = 2 with gt (second half: the masked ranking), else 1.
+ * All three NULL: the counters alone.  1 <= num_classes <= L (the reference: 7).
+ * F3DGS_ERR_UNSUPPORTED: L outside 1..256, H W >= 2^31, N > 65536 views in one call.  F3DGS_ERR_INVALID_ARGUMENT: bad sizes, num_classes out of
+ * range, an unknown format, a NULL teacher, student or counters, a pointer off its element's alignment, only some of the three
+ * outputs or only one carry pointer.  N == 0 is a no-op.  Integer atomics only (32-bit in LDS per workgroup, 64-bit to memory: a
+ * pooled row may pass 2^32): two calls give identical bits.  No host read, no memset; three launches on `stream`: may be captured.
+ *
+ * f3dgs_seg_colorize: the palette pictures of a label map (segmentation.py:547-559).  `labels` N x H x W in any of the three
+ * formats, `palette` L x 3 uint8 on the device, `fill` NULL (black) or 3 bytes in HOST memory: the colour of a label outside
+ * [0, L).  `out` is uint8 N x H x W' x 3:
+ *   F3DGS_SEG_COLOR_MASK   W' = W     palette[label]
+ *   F3DGS_SEG_COLOR_BLEND  W' = W     trunc(255 (a img + b mask)), mask = palette / 255, `image` N x 3 x H x W fp32 in [0, 1]
+ *   F3DGS_SEG_COLOR_STRIP  W' = 3 W   [trunc(255 img) | blend | mask], the reference's `_vis.png`
+ * in the reference's fp32 chain, one rounding per operation and nothing fused: mask = byte / 255.0f, img * a + mask * b,
+ * (uint8) clamp(v * 255.0f, 0, 255), truncated.  The reference casts without the clamp: the clamp only defines images outside
+ * [0, 1] (NaN gives 0).  `image` may be NULL for the mask.  Errors as above (L: F3DGS_ERR_UNSUPPORTED; an unknown mode or
+ * format, a NULL labels, palette, out or needed image: F3DGS_ERR_INVALID_ARGUMENT).  No scratch, no host read, no memset; one
+ * launch on `stream`: may be captured.
+ */
+#define F3DGS_LABELS_U8 0
+#define F3DGS_LABELS_I32 1
+#define F3DGS_LABELS_I64 2
+#define F3DGS_SEG_COLOR_MASK 0
+#define F3DGS_SEG_COLOR_BLEND 1
+#define F3DGS_SEG_COLOR_STRIP 2
+size_t f3dgs_seg_metrics_scratch_bytes(int N, int L, int has_gt);
+int f3dgs_seg_metrics(int N, int H, int W, int L, int num_classes, const void* teacher, int teacher_format, const void* student,
+                      int student_format, const void* gt /* or NULL */, int gt_format,
+                      const int64_t* carry_counts /* A x L or NULL */, const int64_t* carry_scalars /* 5 or NULL */,
+                      int64_t* counters, double* scores, double* iou_per_label, int64_t* labels_ranked,
+                      void* stream /* hipStream_t */);
+int f3dgs_seg_colorize(int N, int H, int W, int L, const void* labels, int labels_format, const unsigned char* palette /* L x 3 */,
+                       const float* image /* N x 3 x H x W or NULL */, int mode, float a, float b,
+                       const unsigned char* fill /* host, 3 bytes, or NULL */, unsigned char* out, void* stream /* hipStream_t */);
+
+/*
  * PCA colour image of a feature map (render.py:38-53, feature_visualize_saving), in two calls around a C x C eigenproblem
  * that is the caller's (feature_pca.py solves it with torch.linalg.eigh in float64).  The (C,HW) map is read by kernels only
  * and nothing of size C*HW is allocated.
