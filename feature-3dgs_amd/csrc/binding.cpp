@@ -562,6 +562,136 @@ torch::Tensor SegColorize(const torch::Tensor& labels, const torch::Tensor& pale
     return out;
 }
 
+// SAM mask post-processing (include/f3dgs.h: f3dgs_sam_masks and what follows it; sam_masks.py checks the arguments and raises
+// ValueError - the checks here guard the pointers).  low_res (M,h,w) float32, iou_preds (M) float32 or None.  Returns (packed
+// (M,FW,ceil(FH/32)) int32, counts (M,3) int32, box (M,4) int32, box_frame (M,4) int32, stability (M) float32, keep (M) bool,
+// kept_index (M) int32, kept_count (1) int32).
+std::vector<torch::Tensor> SamMasks(const torch::Tensor& low_res, const c10::optional<torch::Tensor>& iou_preds, double pred_iou_thresh,
+                                    int64_t S, int64_t ih, int64_t iw, int64_t H, int64_t W, int64_t FH, int64_t FW, int64_t cx0,
+                                    int64_t cy0, double t, double t_hi, double t_lo, double stability_thresh, bool edge_filter) {
+    TORCH_CHECK(low_res.is_cuda() && low_res.scalar_type() == torch::kFloat32 && low_res.dim() == 3,
+                "sam_masks: low_res must be float32 (M,h,w) on a HIP device (no CPU path)");
+    const int64_t M = low_res.size(0);
+    TORCH_CHECK(FH >= 1 && FW >= 1 && FH <= 32768 && FW <= 32768 && M <= 65535, "sam_masks: bad frame or too many masks");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(low_res.device());
+    const torch::Tensor lr = low_res.contiguous();
+    torch::Tensor iou;
+    if (iou_preds.has_value()) {
+        TORCH_CHECK(iou_preds->is_cuda() && iou_preds->device() == low_res.device() && iou_preds->scalar_type() == torch::kFloat32 &&
+                        iou_preds->numel() == M, "sam_masks: iou_preds must be ", M, " float32 values on low_res's device");
+        iou = iou_preds->contiguous();
+    }
+    auto oi = lr.options().dtype(torch::kInt32);
+    const int64_t NW = (FH + 31) / 32;
+    torch::Tensor packed = torch::empty({M, FW, NW}, oi), counts = torch::empty({M, 3}, oi), box = torch::empty({M, 4}, oi);
+    torch::Tensor box_frame = torch::empty({M, 4}, oi), stability = torch::empty({M}, lr.options()), keep = torch::empty({M}, oi.dtype(torch::kBool));
+    torch::Tensor kept_index = torch::empty({M}, oi), kept_count = torch::empty({1}, oi);
+    torch::Tensor scratch = torch::empty({(long long)f3dgs_sam_masks_scratch_bytes((int)M)}, oi.dtype(torch::kByte));
+    const int rc = f3dgs_sam_masks((int)M, (int)lr.size(1), (int)lr.size(2), (int)S, (int)ih, (int)iw, (int)H, (int)W, (int)FH, (int)FW, (int)cx0,
+                                   (int)cy0, M ? lr.data_ptr<float>() : nullptr, iou.defined() && M ? iou.data_ptr<float>() : nullptr,
+                                   (float)pred_iou_thresh, (float)t, (float)t_hi, (float)t_lo, (float)stability_thresh, edge_filter ? 1 : 0,
+                                   reinterpret_cast<uint32_t*>(packed.data_ptr()), counts.data_ptr<int32_t>(), box.data_ptr<int32_t>(),
+                                   box_frame.data_ptr<int32_t>(), stability.data_ptr<float>(),
+                                   reinterpret_cast<unsigned char*>(keep.data_ptr()), kept_index.data_ptr<int32_t>(),
+                                   kept_count.data_ptr<int32_t>(), scratch.data_ptr(), current_stream(lr));
+    check_status(rc, "sam_masks");
+    return {packed, counts, box, box_frame, stability, keep, kept_index, kept_count};
+}
+
+// (M,H,W) float32 v, or bool v > t (f3dgs_sam_upscale)
+torch::Tensor SamUpscale(const torch::Tensor& low_res, int64_t S, int64_t ih, int64_t iw, int64_t H, int64_t W, double t, bool out_bool) {
+    TORCH_CHECK(low_res.is_cuda() && low_res.scalar_type() == torch::kFloat32 && low_res.dim() == 3,
+                "sam_upscale: low_res must be float32 (M,h,w) on a HIP device (no CPU path)");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(low_res.device());
+    const torch::Tensor lr = low_res.contiguous();
+    const int64_t M = lr.size(0);
+    TORCH_CHECK(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "sam_upscale: bad output size");
+    torch::Tensor out = torch::empty({M, H, W}, lr.options().dtype(out_bool ? torch::kBool : torch::kFloat32));
+    const int rc = f3dgs_sam_upscale((int)M, (int)lr.size(1), (int)lr.size(2), (int)S, (int)ih, (int)iw, (int)H, (int)W,
+                                     M ? lr.data_ptr<float>() : nullptr, (float)t, out_bool ? 1 : 0, out.data_ptr(), current_stream(lr));
+    check_status(rc, "sam_upscale");
+    return out;
+}
+
+// boxes (M,4) float32 IN SCORE ORDER, categories (M) int32 or None, order (M) int32 or None.  Returns (keep (M) int32, count (1) int32).
+std::tuple<torch::Tensor, torch::Tensor> BoxNms(const torch::Tensor& boxes, const c10::optional<torch::Tensor>& categories,
+                                                double iou_threshold, const c10::optional<torch::Tensor>& order) {
+    TORCH_CHECK(boxes.is_cuda() && boxes.scalar_type() == torch::kFloat32 && boxes.dim() == 2 && boxes.size(1) == 4,
+                "box_nms: boxes must be float32 (M,4) on a HIP device (no CPU path)");
+    const int64_t M = boxes.size(0);
+    TORCH_CHECK(M <= F3DGS_BOX_NMS_MAX, "box_nms: ", M, " boxes: up to ", F3DGS_BOX_NMS_MAX, " are supported");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(boxes.device());
+    const torch::Tensor b = boxes.contiguous();
+    torch::Tensor cat, ord;
+    for (auto pr : {std::make_pair(&categories, &cat), std::make_pair(&order, &ord)})
+        if (pr.first->has_value()) {
+            const torch::Tensor& v = **pr.first;
+            TORCH_CHECK(v.is_cuda() && v.device() == boxes.device() && v.scalar_type() == torch::kInt32 && v.numel() == M,
+                        "box_nms: categories and order must be ", M, " int32 values on the boxes' device");
+            *pr.second = v.contiguous();
+        }
+    auto oi = b.options().dtype(torch::kInt32);
+    torch::Tensor keep = torch::empty({M}, oi), count = torch::empty({1}, oi);
+    torch::Tensor scratch = torch::empty({(long long)(f3dgs_box_nms_scratch_bytes((int)M) / sizeof(int64_t))}, oi.dtype(torch::kInt64));
+    const int rc = f3dgs_box_nms((int)M, M ? b.data_ptr<float>() : nullptr, cat.defined() && M ? cat.data_ptr<int32_t>() : nullptr,
+                                 (float)iou_threshold, ord.defined() && M ? ord.data_ptr<int32_t>() : nullptr, keep.data_ptr<int32_t>(),
+                                 count.data_ptr<int32_t>(), scratch.data_ptr(), current_stream(b));
+    check_status(rc, "box_nms");
+    return std::make_tuple(keep, count);
+}
+
+static void check_packed(const torch::Tensor& packed, const c10::optional<torch::Tensor>& index, int64_t FH, const char* where) {
+    TORCH_CHECK(packed.is_cuda() && packed.scalar_type() == torch::kInt32 && packed.dim() == 3 && packed.is_contiguous() && FH >= 1 &&
+                    packed.size(2) == (FH + 31) / 32 && packed.size(1) >= 1,
+                where, ": packed must be contiguous int32 (M,FW,ceil(FH/32)) on a HIP device (no CPU path)");
+    if (index.has_value())
+        TORCH_CHECK(index->is_cuda() && index->device() == packed.device() && index->scalar_type() == torch::kInt32 && index->dim() == 1 &&
+                        index->is_contiguous(), where, ": index must be contiguous int32 (K) on the masks' device");
+}
+
+// lens (K) int32 of the masks packed[index] (f3dgs_mask_rle_count)
+torch::Tensor MaskRleCount(const torch::Tensor& packed, const c10::optional<torch::Tensor>& index, int64_t FH) {
+    check_packed(packed, index, FH, "mask_rle_count");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(packed.device());
+    const int64_t K = index.has_value() ? index->numel() : packed.size(0);
+    torch::Tensor lens = torch::empty({K}, packed.options());
+    const int rc = f3dgs_mask_rle_count((int)K, (int)FH, (int)packed.size(1), reinterpret_cast<const uint32_t*>(packed.data_ptr()),
+                                        index.has_value() && K ? index->data_ptr<int32_t>() : nullptr, lens.data_ptr<int32_t>(),
+                                        current_stream(packed));
+    check_status(rc, "mask_rle_count");
+    return lens;
+}
+
+// the counts of every mask into out[head + ends[k] - lens[k] ..), out (head + capacity) int32 (f3dgs_mask_rle_emit)
+void MaskRleEmit(const torch::Tensor& packed, const c10::optional<torch::Tensor>& index, int64_t FH, const torch::Tensor& lens,
+                 const torch::Tensor& ends, torch::Tensor& out, int64_t head) {
+    check_packed(packed, index, FH, "mask_rle_emit");
+    const int64_t K = index.has_value() ? index->numel() : packed.size(0);
+    TORCH_CHECK(lens.is_cuda() && lens.scalar_type() == torch::kInt32 && lens.numel() == K && lens.is_contiguous() && ends.is_cuda() &&
+                    ends.scalar_type() == torch::kInt64 && ends.numel() == K && ends.is_contiguous(),
+                "mask_rle_emit: lens (K) int32 and ends (K) int64 expected");
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kInt32 && out.is_contiguous() && head >= 0 && out.numel() >= head,
+                "mask_rle_emit: out must be contiguous int32 of at least `head` entries");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(packed.device());
+    const int rc = f3dgs_mask_rle_emit((int)K, (int)FH, (int)packed.size(1), reinterpret_cast<const uint32_t*>(packed.data_ptr()),
+                                       index.has_value() && K ? index->data_ptr<int32_t>() : nullptr, lens.data_ptr<int32_t>(),
+                                       ends.data_ptr<int64_t>(), out.numel() - head, out.data_ptr<int32_t>() + head, current_stream(packed));
+    check_status(rc, "mask_rle_emit");
+}
+
+// bool (K,FH,FW) (f3dgs_mask_unpack)
+torch::Tensor MaskUnpack(const torch::Tensor& packed, const c10::optional<torch::Tensor>& index, int64_t FH) {
+    check_packed(packed, index, FH, "mask_unpack");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(packed.device());
+    const int64_t K = index.has_value() ? index->numel() : packed.size(0);
+    torch::Tensor out = torch::empty({K, FH, packed.size(1)}, packed.options().dtype(torch::kBool));
+    const int rc = f3dgs_mask_unpack((int)K, (int)FH, (int)packed.size(1), reinterpret_cast<const uint32_t*>(packed.data_ptr()),
+                                     index.has_value() && K ? index->data_ptr<int32_t>() : nullptr,
+                                     reinterpret_cast<unsigned char*>(out.data_ptr()), current_stream(packed));
+    check_status(rc, "mask_unpack");
+    return out;
+}
+
 // language-guided selection (include/f3dgs.h: f3dgs_edit_select).  features (P, C) float32, contiguous and 16-byte aligned where
 // normalize_inplace asks for the write-back (edit.py copies other views and copies back); text (K, C).  Returns (mask (P),
 // score (P) or None, opacity_out like opacity or None).
@@ -1021,6 +1151,17 @@ PYBIND11_MODULE(_C, m) {
           py::arg("carry_counts"), py::arg("carry_scalars"), py::arg("want_scores"));
     m.def("seg_colorize", &SegColorize, py::arg("labels"), py::arg("palette"), py::arg("image"), py::arg("mode"), py::arg("a"), py::arg("b"),
           py::arg("fill"));
+    m.def("sam_masks", &SamMasks, py::arg("low_res"), py::arg("iou_preds"), py::arg("pred_iou_thresh"), py::arg("S"), py::arg("ih"),
+          py::arg("iw"), py::arg("H"), py::arg("W"), py::arg("FH"), py::arg("FW"), py::arg("cx0"), py::arg("cy0"), py::arg("t"), py::arg("t_hi"),
+          py::arg("t_lo"), py::arg("stability_thresh"), py::arg("edge_filter"));
+    m.def("sam_upscale", &SamUpscale, py::arg("low_res"), py::arg("S"), py::arg("ih"), py::arg("iw"), py::arg("H"), py::arg("W"), py::arg("t"),
+          py::arg("out_bool"));
+    m.def("box_nms", &BoxNms, py::arg("boxes"), py::arg("categories"), py::arg("iou_threshold"), py::arg("order"));
+    m.def("mask_rle_count", &MaskRleCount, py::arg("packed"), py::arg("index"), py::arg("FH"));
+    m.def("mask_rle_emit", &MaskRleEmit, py::arg("packed"), py::arg("index"), py::arg("FH"), py::arg("lens"), py::arg("ends"), py::arg("out"),
+          py::arg("head"));
+    m.def("mask_unpack", &MaskUnpack, py::arg("packed"), py::arg("index"), py::arg("FH"));
+    m.attr("BOX_NMS_MAX") = (int)F3DGS_BOX_NMS_MAX;
     m.attr("LABELS_U8") = (int)F3DGS_LABELS_U8;
     m.attr("LABELS_I32") = (int)F3DGS_LABELS_I32;
     m.attr("LABELS_I64") = (int)F3DGS_LABELS_I64;

@@ -570,6 +570,68 @@ int f3dgs_seg_colorize(int N, int H, int W, int L, const void* labels, int label
                        const unsigned char* fill /* host, 3 bytes, or NULL */, unsigned char* out, void* stream /* hipStream_t */);
 
 /*
+ * SAM mask post-processing: everything between the mask decoder's low-resolution logits and the list of mask records
+ * (encoders/sam_encoder/segment_anything: modeling/sam.py:133-162 postprocess_masks, utils/amg.py calculate_stability_score,
+ * batched_mask_to_box, is_box_near_crop_edge, uncrop_masks, mask_to_rle_pytorch, automatic_mask_generator.py:295-320; and
+ * torchvision's batched_nms).  The networks are not part of this library.
+ *
+ * f3dgs_sam_masks: `low_res` M x h x w fp32 logits.  Per pixel of the H x W crop the reference's value v: resize h x w -> S x S,
+ * keep [:ih, :iw], resize -> H x W, both by PyTorch's upsample_bilinear2d with align_corners = False in fp32, one rounding per
+ * operation: scale = (float)in / out, src = max(scale * (dst + 0.5f) - 0.5f, 0), i1 = i0 + (i0 < in - 1),
+ * l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d); the two stages stay two fp32 results.  v is never stored.  Per mask m:
+ *   counts[m]    = {n_hi, n_lo, area}: the pixels with v > t_hi, v > t_lo, v > t (the caller rounds t + offset and t - offset to fp32)
+ *   box[m]       = XYXY min / max of the columns and rows with a set pixel, in the crop's frame; {0, 0, 0, 0} for an empty mask
+ *   box_frame[m] = box + (cx0, cy0, cx0, cy0)
+ *   stability[m] = (float)n_hi / (float)n_lo, IEEE; 0 / 0 = NaN
+ *   packed       M x FW x ceil(FH / 32) words, the mask v > t in the FULL FH x FW frame, column-major: word (x, y / 32) holds rows
+ *                32 (y / 32) .. + 31 of column x, bit = row % 32; rows >= FH and everything outside the crop (its origin
+ *                (cx0, cy0), its size H x W, inside the frame) are zero.  Every word is written: no clear is needed.
+ *   keep[m]      = iou ok and (stability_thresh <= 0 or stability >= stability_thresh) and not (edge_filter and near the crop's
+ *                edge): a box coordinate within 20 of the crop's but not within 20 of the frame's (is_box_near_crop_edge)
+ *   kept_index   the m with keep[m], ascending, then -1; *kept_count their number
+ * iou ok: pred_iou_thresh <= 0 or iou_preds == NULL, or iou_preds[m] > pred_iou_thresh (strict; NaN fails).  A mask that fails
+ * is skipped: its workgroups write zero words and return, its counts are 0, its box 0, its stability NaN.
+ * `scratch`: f3dgs_sam_masks_scratch_bytes(M) bytes, 4-byte aligned, uninitialised.  Three launches (two for M == 0, which gives
+ * *kept_count = 0), integer atomics only: two calls give identical bits.  No host read, no memset: may be captured.
+ * F3DGS_ERR_INVALID_ARGUMENT: bad sizes, ih or iw > S, a crop outside the frame, a NULL pointer.  F3DGS_ERR_UNSUPPORTED: M > 65535,
+ * a size > 32768, FH FW > 2^30.
+ *
+ * f3dgs_sam_upscale: the same v for every pixel, stored: `out` M x H x W fp32, or with out_bool bytes v > t (the drop-in for
+ * postprocess_masks and the threshold that follows it).  One launch.
+ *
+ * f3dgs_box_nms: greedy non-maximum suppression of M <= F3DGS_BOX_NMS_MAX boxes GIVEN IN SCORE ORDER (`boxes` M x 4 fp32 XYXY,
+ * best first): box j is suppressed when an earlier KEPT box i of the same category (`categories` M int32 or NULL: all one) has
+ * IoU > iou_threshold (strict), IoU = inter / (area_i + area_j - inter) in fp32 with an IEEE division, inter from widths clamped
+ * at 0, no +1; a NaN quotient (two empty boxes) never suppresses.  `keep` receives the kept positions in score order - order[i]
+ * instead of i where `order` (M int32, the sort's permutation) is given - then -1; *count their number.  `scratch`:
+ * f3dgs_box_nms_scratch_bytes(M) bytes (the M x ceil(M / 64) suppression words), 8-byte aligned.  Two launches, no host read.
+ *
+ * f3dgs_mask_rle_count / _emit: the reference's uncompressed RLE of K packed masks (`index` K int32 rows of `packed`, or NULL:
+ * rows 0 .. K - 1): runs down the columns, continuing across column ends, a leading 0 where pixel (0, 0) is set.  _count writes
+ * lens[k], the number of counts of mask k.  _emit takes `ends`, the INCLUSIVE prefix sums of lens (int64), and writes the counts
+ * of mask k to out[ends[k] - lens[k] ..) where they end within `capacity` entries (a mask that does not fit is left out whole:
+ * the caller compares ends[K - 1] with capacity).  f3dgs_mask_unpack: K x FH x FW bytes 0 / 1.  One launch each.
+ */
+#define F3DGS_BOX_NMS_MAX 16384
+size_t f3dgs_sam_masks_scratch_bytes(int M);
+int f3dgs_sam_masks(int M, int h, int w, int S, int ih, int iw, int H, int W, int FH, int FW, int cx0, int cy0, const float* low_res,
+                    const float* iou_preds /* M or NULL */, float pred_iou_thresh, float t, float t_hi, float t_lo,
+                    float stability_thresh, int edge_filter, uint32_t* packed, int32_t* counts /* M x 3 */, int32_t* box /* M x 4 */,
+                    int32_t* box_frame /* M x 4 */, float* stability, unsigned char* keep, int32_t* kept_index, int32_t* kept_count,
+                    void* scratch, void* stream /* hipStream_t */);
+int f3dgs_sam_upscale(int M, int h, int w, int S, int ih, int iw, int H, int W, const float* low_res, float t, int out_bool, void* out,
+                      void* stream /* hipStream_t */);
+size_t f3dgs_box_nms_scratch_bytes(int M);
+int f3dgs_box_nms(int M, const float* boxes, const int32_t* categories /* or NULL */, float iou_threshold,
+                  const int32_t* order /* or NULL */, int32_t* keep, int32_t* count, void* scratch, void* stream /* hipStream_t */);
+int f3dgs_mask_rle_count(int K, int FH, int FW, const uint32_t* packed, const int32_t* index /* or NULL */, int32_t* lens,
+                         void* stream /* hipStream_t */);
+int f3dgs_mask_rle_emit(int K, int FH, int FW, const uint32_t* packed, const int32_t* index /* or NULL */, const int32_t* lens,
+                        const int64_t* ends, int64_t capacity, int32_t* out, void* stream /* hipStream_t */);
+int f3dgs_mask_unpack(int K, int FH, int FW, const uint32_t* packed, const int32_t* index /* or NULL */, unsigned char* out,
+                      void* stream /* hipStream_t */);
+
+/*
  * PCA colour image of a feature map (render.py:38-53, feature_visualize_saving), in two calls around a C x C eigenproblem
  * that is the caller's (feature_pca.py solves it with torch.linalg.eigh in float64).  The (C,HW) map is read by kernels only
  * and nothing of size C*HW is allocated.
