@@ -692,6 +692,30 @@ torch::Tensor MaskUnpack(const torch::Tensor& packed, const c10::optional<torch:
     return out;
 }
 
+// remove_small_regions of the masks packed[index] (f3dgs_mask_regions).  Returns (words (K,FW,NW) int32, changed (K) bool, area (K)
+// int32, box (K,4) int32, runs): where runs > run_capacity the tensors are unwritten and the caller comes again.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int64_t>
+MaskRegions(const torch::Tensor& packed, const c10::optional<torch::Tensor>& index, int64_t FH, double area_thresh, bool holes,
+            int64_t run_capacity) {
+    check_packed(packed, index, FH, "mask_regions");
+    TORCH_CHECK(run_capacity >= 0 && run_capacity <= 2147483647LL, "mask_regions: run_capacity out of range");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(packed.device());
+    const int64_t K = index.has_value() ? index->numel() : packed.size(0);
+    const int64_t FW = packed.size(1);
+    TORCH_CHECK(K <= 65535 && FH <= 32768 && FW <= 32768, "mask_regions: up to 65535 masks of up to 32768 a side are supported");
+    auto oi = packed.options();
+    torch::Tensor out = torch::empty({K, FW, packed.size(2)}, oi), changed = torch::empty({K}, oi.dtype(torch::kBool));
+    torch::Tensor area = torch::empty({K}, oi), box = torch::empty({K, 4}, oi);
+    torch::Tensor scratch = torch::empty({(long long)((f3dgs_mask_regions_scratch_bytes((int)K, (int)FW, run_capacity) + 7) / 8)}, oi.dtype(torch::kInt64));
+    int64_t runs = 0;
+    const int rc = f3dgs_mask_regions((int)K, (int)FH, (int)FW, reinterpret_cast<const uint32_t*>(packed.data_ptr()),
+                                      index.has_value() && K ? index->data_ptr<int32_t>() : nullptr, holes ? 1 : 0, area_thresh, run_capacity,
+                                      reinterpret_cast<uint32_t*>(out.data_ptr()), reinterpret_cast<unsigned char*>(changed.data_ptr()),
+                                      area.data_ptr<int32_t>(), box.data_ptr<int32_t>(), &runs, scratch.data_ptr(), current_stream(packed));
+    check_status(rc, "mask_regions");
+    return std::make_tuple(out, changed, area, box, runs);
+}
+
 // language-guided selection (include/f3dgs.h: f3dgs_edit_select).  features (P, C) float32, contiguous and 16-byte aligned where
 // normalize_inplace asks for the write-back (edit.py copies other views and copies back); text (K, C).  Returns (mask (P),
 // score (P) or None, opacity_out like opacity or None).
@@ -1161,6 +1185,8 @@ PYBIND11_MODULE(_C, m) {
     m.def("mask_rle_emit", &MaskRleEmit, py::arg("packed"), py::arg("index"), py::arg("FH"), py::arg("lens"), py::arg("ends"), py::arg("out"),
           py::arg("head"));
     m.def("mask_unpack", &MaskUnpack, py::arg("packed"), py::arg("index"), py::arg("FH"));
+    m.def("mask_regions", &MaskRegions, py::arg("packed"), py::arg("index"), py::arg("FH"), py::arg("area_thresh"), py::arg("holes"),
+          py::arg("run_capacity"));
     m.attr("BOX_NMS_MAX") = (int)F3DGS_BOX_NMS_MAX;
     m.attr("LABELS_U8") = (int)F3DGS_LABELS_U8;
     m.attr("LABELS_I32") = (int)F3DGS_LABELS_I32;

@@ -16,9 +16,13 @@ Replaces what the reference runs after the decoder (encoders/sam_encoder/segment
     masks = upscale_masks(low_res, 1024, (576, 1024), (1080, 1920))              # the drop-in for postprocess_masks
     keep, count = box_nms(boxes, scores, 0.7);  keep = batched_nms(boxes, scores, idxs, 0.7)
     rles = masks_to_rle(st.packed, st.kept_index[:k]);  dense = unpack_masks(st.packed, index)
-    pp = MaskPostprocessor((1080, 1920));  pp.add_batch(...);  records = pp.finish()      # SamAutomaticMaskGenerator.generate's records
+    new, changed = remove_small_regions(st.packed, 100, "holes", index)          # utils/amg.py:remove_small_regions, K masks at once
+    sr = postprocess_small_regions(st.packed, 100, index)                        # holes, then islands: packed, changed, area, box
+    pp = MaskPostprocessor((1080, 1920), min_mask_region_area=100);  pp.add_batch(...);  records = pp.finish()      # generate's records
 
-csrc/sam_masks.hip behind include/f3dgs.h (f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_*, f3dgs_mask_unpack).
+csrc/sam_masks.hip and csrc/mask_regions.hip behind include/f3dgs.h (f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms,
+f3dgs_mask_rle_*, f3dgs_mask_unpack, f3dgs_mask_regions).  The small-region removal labels the bit-packed masks where they lie:
+its nodes are the vertical runs of a column, joined by a union-find of integer atomics; no dense label image, no OpenCV.
 Both resizes are PyTorch's upsample_bilinear2d (align_corners=False) in fp32, one rounding per operation, kept as two stages;
 counts, boxes and bits are integers, the stability score one IEEE division: two calls give the same bits.  The networks (image
 encoder, prompt encoder, mask decoder) are not part of this project.
@@ -40,6 +44,8 @@ OUTPUT_MODES = ("uncompressed_rle", "binary_mask")
 PackedMasks = namedtuple("PackedMasks", ["words", "frame_size"])
 PackedMasks.__doc__ = """words: int32 (M, FW, ceil(FH / 32)) - word (x, y // 32) holds rows 32 (y // 32) .. + 31 of column x, bit = row % 32;
 frame_size: (FH, FW)."""
+SmallRegions = namedtuple("SmallRegions", ["packed", "changed", "area", "box"])
+REGION_MODES = ("holes", "islands")
 MaskStats = namedtuple("MaskStats", ["n_hi", "n_lo", "area", "box", "box_frame", "stability", "packed", "keep", "kept_index", "kept_count"])
 
 
@@ -271,6 +277,55 @@ def unpack_masks(packed, index=None) -> torch.Tensor:
     return _C().mask_unpack(w, index, FH)
 
 
+# ---- small regions ----------------------------------------------------------------------------------------------------------
+def _area(v, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)) or float(v) < 0:
+        raise ValueError(f"{name} {v!r}: a finite number >= 0 expected")
+    return float(v)
+
+
+def _label(w, index, FH, FW, thresh, holes):
+    """One labelling: (words, changed, area, box).  The run buffers are sized before the runs are known, at 4 FW + 64 per mask (a
+    blob has about 2 per column, its background about 2 FW); the call's one host read brings the number back, and only masks
+    that outgrow the provision cost a second call."""
+    K = w.shape[0] if index is None else index.shape[0]
+    capacity = K * (4 * FW + 64)
+    *out, runs = _C().mask_regions(w, index, FH, thresh, holes, capacity)
+    if runs > capacity:
+        *out, runs = _C().mask_regions(w, index, FH, thresh, holes, runs)
+    return out
+
+
+@torch.no_grad()
+def remove_small_regions(packed, area_thresh, mode, index=None):
+    """utils/amg.py:remove_small_regions of the K masks packed[index] (all, without index) at once: (PackedMasks, changed (K,) bool).
+    mode "holes": the 8-connected components of the BACKGROUND with area < area_thresh (strict; the outer background counts) are
+    filled.  mode "islands": the foreground components with area < area_thresh are dropped - but where every one is small the
+    largest stays, and changed is True all the same (one island below the threshold: the same bits, changed).  changed is False,
+    and the bits are the input's, where no component is small.  Ties for the largest go to the component whose first pixel comes
+    first in row-major order: this project's rule (scipy.ndimage.label's label order), not measured against OpenCV.  packed is
+    only read.  One host read (the number of runs, with the kernels' error word), a second call and read only where the masks
+    have more than 4 FW + 64 runs each."""
+    thresh = _area(area_thresh, "area_thresh")
+    if mode not in REGION_MODES:
+        raise ValueError(f"mode {mode!r}: one of {', '.join(REGION_MODES)} expected")
+    w, index, FH, FW = _packed_args(packed, index, "the regions are labelled")
+    words, changed, _, _ = _label(w, index, FH, FW, thresh, mode == "holes")
+    return PackedMasks(words, (FH, FW)), changed
+
+
+@torch.no_grad()
+def postprocess_small_regions(packed, min_area, index=None) -> SmallRegions:
+    """What automatic_mask_generator.py:postprocess_small_regions does to every mask: holes, then islands on the result.
+    SmallRegions(packed, changed (K,) bool = either pass changed, area (K,) int32 and box (K,4) int32 XYXY of the new masks in
+    the full frame, [0,0,0,0] when empty - both from the launch that writes the words).  One host read per labelling: two."""
+    thresh = _area(min_area, "min_area")
+    w, index, FH, FW = _packed_args(packed, index, "the regions are labelled")
+    filled, changed_h, _, _ = _label(w, index, FH, FW, thresh, True)
+    words, changed_i, area, box = _label(filled, None, FH, FW, thresh, False)
+    return SmallRegions(PackedMasks(words, (FH, FW)), changed_h | changed_i, area, box)
+
+
 # ---- the assembled pipeline -------------------------------------------------------------------------------------------------
 class MaskPostprocessor:
     """The records of SamAutomaticMaskGenerator.generate from the decoder's outputs:
@@ -284,10 +339,14 @@ class MaskPostprocessor:
     add_batch runs the fused pass and the filter and keeps their device tensors: no host read.  finish() reads the kept lists
     once, runs the box NMS of every crop (scores iou_preds, box_nms_thresh; one read of the count per crop, as torchvision's has)
     and, with more than one crop, the NMS across crops (scores 1 / crop area, crop_nms_thresh), then reads the survivors' scalars
-    once and their run lengths once.  Not built: postprocess_small_regions (min_mask_region_area > 0) and coco_rle."""
+    once and their run lengths once.  With min_mask_region_area > 0 the survivors first go through postprocess_small_regions
+    (two labellings, one host read each) and a second NMS at max(box_nms_thresh, crop_nms_thresh) on the new masks' boxes with
+    score 1 for an unchanged mask and 0 for a changed one (this project's box_nms: stable, the lower row first among equal
+    scores); a kept changed mask takes its new bits, box and area, and the records come out unchanged masks first, then the
+    changed ones, each group in its former order.  Not built: coco_rle."""
 
     def __init__(self, frame_size, *, pred_iou_thresh=0.88, stability_score_thresh=0.95, stability_score_offset=1.0, box_nms_thresh=0.7,
-                 crop_nms_thresh=0.7, mask_threshold=0.0, output_mode="uncompressed_rle"):
+                 crop_nms_thresh=0.7, mask_threshold=0.0, output_mode="uncompressed_rle", min_mask_region_area=0):
         self.frame_size = _pair(frame_size, "frame_size")
         if output_mode not in OUTPUT_MODES:
             raise ValueError(f"output_mode {output_mode!r}: one of {', '.join(OUTPUT_MODES)} expected (coco_rle needs pycocotools and is not built)")
@@ -298,6 +357,7 @@ class MaskPostprocessor:
         self.crop_nms_thresh = _number(crop_nms_thresh, "crop_nms_thresh")
         self.mask_threshold = _number(mask_threshold, "mask_threshold")
         self.output_mode = output_mode
+        self.min_mask_region_area = _area(min_mask_region_area, "min_mask_region_area")
         self._batches = []
 
     def add_batch(self, low_res, iou_preds, points, crop_box, input_size, original_size, img_size):
@@ -357,13 +417,32 @@ class MaskPostprocessor:
         if K == 0:
             return []
         stats = cat(lambda b: torch.cat([b[0].area[:, None].double(), b[0].stability[:, None].double()], 1))
-        table = torch.cat([box_frame[g].double(), iou[g][:, None].double(), stats[g]], 1).cpu().numpy()      # host read of the scalars
-        rows = g.cpu().numpy()
-        which = np.searchsorted(offsets, rows, side="right") - 1
-        words = torch.empty((K,) + tuple(batches[0][0].packed.words.shape[1:]), dtype=torch.int32, device=dev)
-        for b in np.unique(which):
-            sel = np.nonzero(which == b)[0]
-            words[torch.as_tensor(sel, device=dev)] = batches[b][0].packed.words[torch.as_tensor(rows[sel] - offsets[b], device=dev)]
+
+        def gather(rows):
+            which = np.searchsorted(offsets, rows, side="right") - 1
+            words = torch.empty((len(rows),) + tuple(batches[0][0].packed.words.shape[1:]), dtype=torch.int32, device=dev)
+            for b in np.unique(which):
+                sel = np.nonzero(which == b)[0]
+                words[torch.as_tensor(sel, device=dev)] = batches[b][0].packed.words[torch.as_tensor(rows[sel] - offsets[b], device=dev)]
+            return words
+
+        if self.min_mask_region_area > 0:
+            # automatic_mask_generator.py:postprocess_small_regions, before any scalar or run length is read
+            sr = postprocess_small_regions(PackedMasks(gather(g.cpu().numpy()), self.frame_size), self.min_mask_region_area)
+            keep = batched_nms(sr.box, (~sr.changed).to(torch.float32), torch.zeros(K, dtype=torch.int32, device=dev),
+                               max(self.box_nms_thresh, self.crop_nms_thresh))
+            g, ch = g[keep], sr.changed[keep]
+            crop_of = [crop_of[i] for i in keep.tolist()]
+            K = g.shape[0]
+            words = torch.where(ch[:, None, None], sr.packed.words[keep], gather(g.cpu().numpy()))
+            new_box = torch.where(ch[:, None], sr.box[keep], box_frame[g]).double()
+            new_stats = torch.cat([torch.where(ch, sr.area[keep], stats[g][:, 0].to(torch.int32))[:, None].double(), stats[g][:, 1:]], 1)
+            table = torch.cat([new_box, iou[g][:, None].double(), new_stats], 1).cpu().numpy()                # host read of the scalars
+            rows = g.cpu().numpy()
+        else:
+            table = torch.cat([box_frame[g].double(), iou[g][:, None].double(), stats[g]], 1).cpu().numpy()  # host read of the scalars
+            rows = g.cpu().numpy()
+            words = gather(rows)
         packed = PackedMasks(words, self.frame_size)
         if self.output_mode == "binary_mask":
             seg = list(unpack_masks(packed).cpu().numpy())

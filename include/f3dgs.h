@@ -611,6 +611,25 @@ int f3dgs_seg_colorize(int N, int H, int W, int L, const void* labels, int label
  * lens[k], the number of counts of mask k.  _emit takes `ends`, the INCLUSIVE prefix sums of lens (int64), and writes the counts
  * of mask k to out[ends[k] - lens[k] ..) where they end within `capacity` entries (a mask that does not fit is left out whole:
  * the caller compares ends[K - 1] with capacity).  f3dgs_mask_unpack: K x FH x FW bytes 0 / 1.  One launch each.
+ *
+ * f3dgs_mask_regions: utils/amg.py remove_small_regions (automatic_mask_generator.py:325-373 calls it twice per mask) of K packed
+ * masks (`index` as above; `packed` is only read).  `holes` != 0 labels the background (clear bits of rows < FH), 0 the foreground,
+ * with 8-connectivity; a component is small when its area < area_thresh (strict, a double).  `changed`[k] = 1 iff mask k has a
+ * small component.  `out` K x FW x ceil(FH / 32) words: with holes the mask OR its small background components (the outer
+ * background included); without, the mask without its small components - but where EVERY component is small the largest stays
+ * (`changed` is 1 all the same); ties for the largest go to the component whose first pixel comes first in row-major order.
+ * Rows >= FH of `out` are zero whatever `packed` holds there.  area[k] = the set pixels of out[k], box[k] (K x 4) its XYXY
+ * min / max columns and rows, {0, 0, 0, 0} when empty: both come from the launch that writes the words.
+ * No dense label image: the nodes are the maximal vertical runs of the labelled polarity within a column, 16 bytes each, joined
+ * by a union-find of integer atomics whose roots are the smallest run of a component; two calls give identical bits.
+ * `scratch`: f3dgs_mask_regions_scratch_bytes(K, FW, run_capacity) bytes, 8-byte aligned, uninitialised.  *runs (a HOST int64)
+ * receives the number of runs; where it exceeds run_capacity NOTHING is written to out, changed, area or box and the call
+ * returns F3DGS_OK: the caller compares and comes again with room (a blob has about 2 runs per column, its background about 2 FW).
+ * Seven launches (six for FW == 1), then ONE host read (the total and the error word together: the call synchronises `stream`
+ * and cannot be captured).  Every loop is bounded by construction; the walks of the union-find also carry a cap of the number
+ * of runs, and a walk that reaches it makes the call return F3DGS_ERR_HIP.  F3DGS_ERR_INVALID_ARGUMENT: bad sizes, area_thresh
+ * negative or not finite, a NULL pointer, a misaligned scratch.  F3DGS_ERR_UNSUPPORTED: K > 65535, an edge > 32768,
+ * FH FW > 2^30, run_capacity >= 2^31.
  */
 #define F3DGS_BOX_NMS_MAX 16384
 size_t f3dgs_sam_masks_scratch_bytes(int M);
@@ -630,6 +649,10 @@ int f3dgs_mask_rle_emit(int K, int FH, int FW, const uint32_t* packed, const int
                         const int64_t* ends, int64_t capacity, int32_t* out, void* stream /* hipStream_t */);
 int f3dgs_mask_unpack(int K, int FH, int FW, const uint32_t* packed, const int32_t* index /* or NULL */, unsigned char* out,
                       void* stream /* hipStream_t */);
+size_t f3dgs_mask_regions_scratch_bytes(int K, int FW, int64_t run_capacity);
+int f3dgs_mask_regions(int K, int FH, int FW, const uint32_t* packed, const int32_t* index /* or NULL */, int holes, double area_thresh,
+                       int64_t run_capacity, uint32_t* out, unsigned char* changed, int32_t* area, int32_t* box /* K x 4 */,
+                       int64_t* runs /* host */, void* scratch, void* stream /* hipStream_t */);
 
 /*
  * PCA colour image of a feature map (render.py:38-53, feature_visualize_saving), in two calls around a C x C eigenproblem
