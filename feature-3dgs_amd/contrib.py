@@ -15,6 +15,14 @@ model, of this package's own `segment()`, of a click in the viewer - to the `mas
         lifter.add_view(cam, gaussians, pipe, bg, masks_of(cam))        # (K, H, W) bool / uint8 / float
     edit.apply_edit(opacity, shs, lifter.select(0.5)[:, k], {"deletion": True})
 
+A label map - one class per pixel, as segment() or sam_masks.instance_map() give it - is lifted in ONE walk per view however many
+classes it has (f3dgs_label_votes), without the (L, H, W) one-hot stack:
+
+    lifter = LabelLifter(P, 150, device)
+    for cam in cameras:
+        lifter.add_view(cam, gaussians, pipe, bg, label_map_of(cam))    # (H, W) uint8 / int32 / int64
+    edit.apply_edit(opacity, shs, lifter.select(cls), {"deletion": True});  picture = lifter.label_image(ids)
+
 HIP only; no CPU fallback.  Nothing is read back to the host.
 """
 from __future__ import annotations
@@ -26,6 +34,8 @@ import torch
 from diff_gaussian_rasterization import _C, GaussianRasterizationSettings
 
 MAX_MASKS = 7           # F3DGS_CONTRIB_MAX_MASKS: mask columns one walk carries (more are taken in groups)
+MAX_LABELS = 65536      # F3DGS_LABEL_VOTES_MAX_LABELS: classes of a label vote
+LABEL_DTYPES = (torch.uint8, torch.int32, torch.int64)
 
 
 def _need_device(t, name):
@@ -63,6 +73,32 @@ def _check_acc(acc, wmax, P, K, dev):
                              f"on {wmax.device}")
 
 
+def _check_gaussians(means3D, shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """The argument rules of the rasterizer's forward call; returns (P, device)."""
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise ValueError(f"means3D (P, 3) expected, got {tuple(means3D.shape)}")
+    if (shs is None) == (colors_precomp is None):
+        raise ValueError("provide exactly one of shs and colors_precomp")
+    if (scales is None or rotations is None) == (cov3D_precomp is None) or ((scales is None) != (rotations is None)):
+        raise ValueError("provide exactly one of the scales / rotations pair and cov3D_precomp")
+    _need_device(means3D, "means3D")
+    return means3D.shape[0], means3D.device
+
+
+def _forward(rs, means3D, opacities, shs, colors_precomp, semantic_feature, scales, rotations, cov3D_precomp):
+    """One forward call of the rasterizer (the caller holds no_grad): render, feature_map, depth, radii and the state tuple
+    (geom, binning, img, P, num_rendered, H, W) the passes take."""
+    P, H, W = means3D.shape[0], int(rs.image_height), int(rs.image_width)
+    empty = torch.Tensor([])
+    opt = lambda t: empty if t is None else t.detach()
+    feat = means3D.new_zeros((P, 1, 0)) if semantic_feature is None else semantic_feature.detach()
+    (num_rendered, color, feature_map, depth, radii, geom, binning, img) = _C.rasterize_gaussians(
+        rs.bg, means3D.detach(), opt(colors_precomp), feat, opacities.detach(), opt(scales), opt(rotations), rs.scale_modifier,
+        opt(cov3D_precomp), rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, opt(shs), rs.sh_degree, rs.campos,
+        rs.prefiltered, rs.debug)
+    return color, feature_map, depth, radii, (geom, binning, img, P, num_rendered, H, W)
+
+
 def contributions(raster_settings, *, means3D, opacities, shs=None, colors_precomp=None, semantic_feature=None, scales=None,
                   rotations=None, cov3D_precomp=None, masks=None, acc=None, wmax=None, pixel_outputs=True) -> dict:
     """One forward call of the rasterizer and the contribution pass over its state, under no_grad.
@@ -74,14 +110,7 @@ def contributions(raster_settings, *, means3D, opacities, shs=None, colors_preco
     Returns render, feature_map, depth, radii and alpha, median_depth, ids, id_weight, acc, wmax (None where not asked for)."""
     rs = raster_settings
     H, W = int(rs.image_height), int(rs.image_width)
-    if means3D.dim() != 2 or means3D.shape[1] != 3:
-        raise ValueError(f"means3D (P, 3) expected, got {tuple(means3D.shape)}")
-    if (shs is None) == (colors_precomp is None):
-        raise ValueError("provide exactly one of shs and colors_precomp")
-    if (scales is None or rotations is None) == (cov3D_precomp is None) or ((scales is None) != (rotations is None)):
-        raise ValueError("provide exactly one of the scales / rotations pair and cov3D_precomp")
-    _need_device(means3D, "means3D")
-    P, dev = means3D.shape[0], means3D.device
+    P, dev = _check_gaussians(means3D, shs, colors_precomp, scales, rotations, cov3D_precomp)
     masks = _check_masks(masks, H, W, dev)
     K = 0 if masks is None else masks.shape[0]
     if acc is None and masks is not None:
@@ -91,14 +120,8 @@ def contributions(raster_settings, *, means3D, opacities, shs=None, colors_preco
         raise ValueError("nothing asked for: no masks, no acc, no wmax and pixel_outputs=False")
 
     with torch.no_grad():
-        empty = torch.Tensor([])
-        opt = lambda t: empty if t is None else t.detach()
-        feat = means3D.new_zeros((P, 1, 0)) if semantic_feature is None else semantic_feature.detach()
-        (num_rendered, color, feature_map, depth, radii, geom, binning, img) = _C.rasterize_gaussians(
-            rs.bg, means3D.detach(), opt(colors_precomp), feat, opacities.detach(), opt(scales), opt(rotations), rs.scale_modifier,
-            opt(cov3D_precomp), rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, opt(shs), rs.sh_degree, rs.campos,
-            rs.prefiltered, rs.debug)
-        state = (geom, binning, img, P, num_rendered, H, W)
+        color, feature_map, depth, radii, state = _forward(rs, means3D, opacities, shs, colors_precomp, semantic_feature, scales,
+                                                           rotations, cov3D_precomp)
         pix = (None, None, None, None)
         if K <= MAX_MASKS:
             pix = _C.contributions(*state, masks if K else None, acc, wmax, bool(pixel_outputs))
@@ -117,10 +140,8 @@ def contributions(raster_settings, *, means3D, opacities, shs=None, colors_preco
             "ids": pix[2], "id_weight": pix[3], "acc": acc, "wmax": wmax}
 
 
-def render_contributions(viewpoint_camera, pc, pipe, bg_color, masks=None, acc=None, wmax=None, pixel_outputs=True,
-                         scaling_modifier=1.0, override_color=None) -> dict:
-    """`contributions` with the argument conventions of the reference's render() (gaussian_renderer/__init__.py:173):
-    camera, Gaussian model, pipeline flags, background."""
+def _render_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color):
+    """The raster settings and the Gaussian arguments of the reference's render() (gaussian_renderer/__init__.py:173)."""
     raster_settings = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
@@ -144,9 +165,68 @@ def render_contributions(viewpoint_camera, pc, pipe, bg_color, masks=None, acc=N
             shs = pc.get_features
     else:
         colors_precomp = override_color
-    return contributions(raster_settings, means3D=pc.get_xyz, opacities=pc.get_opacity, shs=shs, colors_precomp=colors_precomp,
-                         semantic_feature=pc.get_semantic_feature, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp,
-                         masks=masks, acc=acc, wmax=wmax, pixel_outputs=pixel_outputs)
+    return raster_settings, dict(means3D=pc.get_xyz, opacities=pc.get_opacity, shs=shs, colors_precomp=colors_precomp,
+                                 semantic_feature=pc.get_semantic_feature, scales=scales, rotations=rotations,
+                                 cov3D_precomp=cov3D_precomp)
+
+
+def render_contributions(viewpoint_camera, pc, pipe, bg_color, masks=None, acc=None, wmax=None, pixel_outputs=True,
+                         scaling_modifier=1.0, override_color=None) -> dict:
+    """`contributions` with the argument conventions of the reference's render() (gaussian_renderer/__init__.py:173):
+    camera, Gaussian model, pipeline flags, background."""
+    raster_settings, kw = _render_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color)
+    return contributions(raster_settings, masks=masks, acc=acc, wmax=wmax, pixel_outputs=pixel_outputs, **kw)
+
+
+def _check_labels(labels, H, W, dev):
+    if not torch.is_tensor(labels) or labels.dtype not in LABEL_DTYPES or tuple(labels.shape) != (H, W):
+        got = f"{labels.dtype} {tuple(labels.shape)}" if torch.is_tensor(labels) else type(labels).__name__
+        raise ValueError(f"labels: a uint8, int32 or int64 ({H}, {W}) tensor expected (a map of another size is the caller's to "
+                         f"resize), got {got}")
+    _need_device(labels, "labels")
+    if labels.device != dev:
+        raise ValueError(f"labels on {labels.device}, the Gaussians on {dev}")
+    return labels.detach().contiguous()
+
+
+def _check_votes(acc, P, L, dev):
+    _need_device(acc, "acc")
+    if acc.dtype != torch.float32 or not acc.is_contiguous() or tuple(acc.shape) != (P, L + 1) or acc.device != dev:
+        raise ValueError(f"acc must be a contiguous float32 ({P}, {L + 1}) tensor on {dev} (one column per class and the weight "
+                         f"total), got {acc.dtype} {tuple(acc.shape)} on {acc.device}")
+
+
+def label_votes(raster_settings, *, means3D, opacities, shs=None, colors_precomp=None, semantic_feature=None, scales=None,
+                rotations=None, cov3D_precomp=None, labels, num_classes, acc=None) -> dict:
+    """One forward call of the rasterizer and the label vote over its state, under no_grad: what `contributions` gives for
+    masks=MaskLifter.from_label_map(labels, num_classes), in ONE walk whatever num_classes is and without the one-hot stack.
+
+    labels: (H, W) uint8 / int32 / int64 on the Gaussians' device, e.g. the map of segment() (at the view's size: a map of
+    another size is the caller's to resize) or sam_masks.instance_map(); a label outside [0, num_classes) belongs to no class
+    but counts in the weight total.  acc: (P, num_classes + 1) float32, ADDED to (the last column: the weight total); made of
+    zeros when not given.  Returns render, feature_map, depth, radii and acc."""
+    rs = raster_settings
+    H, W = int(rs.image_height), int(rs.image_width)
+    P, dev = _check_gaussians(means3D, shs, colors_precomp, scales, rotations, cov3D_precomp)
+    L = int(num_classes)
+    if not 1 <= L <= MAX_LABELS:
+        raise ValueError(f"num_classes = {num_classes}: 1 .. {MAX_LABELS} expected")
+    labels = _check_labels(labels, H, W, dev)
+    if acc is None:
+        acc = torch.zeros(P, L + 1, device=dev, dtype=torch.float32)
+    _check_votes(acc, P, L, dev)
+    with torch.no_grad():
+        color, feature_map, depth, radii, state = _forward(rs, means3D, opacities, shs, colors_precomp, semantic_feature, scales,
+                                                           rotations, cov3D_precomp)
+        _C.label_votes(*state, labels, L, acc)
+    return {"render": color, "feature_map": feature_map, "depth": depth, "radii": radii, "acc": acc}
+
+
+def render_label_votes(viewpoint_camera, pc, pipe, bg_color, labels, num_classes, acc=None, scaling_modifier=1.0,
+                       override_color=None) -> dict:
+    """`label_votes` with the argument conventions of the reference's render(), as render_contributions."""
+    raster_settings, kw = _render_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color)
+    return label_votes(raster_settings, labels=labels, num_classes=num_classes, acc=acc, **kw)
 
 
 class MaskLifter:
@@ -204,4 +284,67 @@ class MaskLifter:
         return (label_map[None] == classes[:, None, None]).to(torch.float32)
 
 
-__all__ = ["MAX_MASKS", "contributions", "render_contributions", "MaskLifter"]
+class LabelLifter:
+    """Labels the P Gaussians in 3D from label maps of L classes seen in any number of views: per Gaussian the blend weight that
+    fell on each class, summed over the views - one walk per view (f3dgs_label_votes), whatever L is."""
+
+    def __init__(self, P: int, L: int, device):
+        if P < 0 or not 1 <= L <= MAX_LABELS:
+            raise ValueError(f"LabelLifter(P={P}, L={L}): P >= 0 and 1 <= L <= {MAX_LABELS} expected")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"LabelLifter needs a HIP device (got {device}): the label vote has no CPU path")
+        self.P, self.L = int(P), int(L)
+        self.acc = torch.zeros(self.P, self.L + 1, device=device, dtype=torch.float32)
+        self.views = 0
+
+    def add_view(self, viewpoint_camera, pc, pipe, bg_color, label_map, scaling_modifier=1.0, override_color=None) -> dict:
+        """Accumulates one view's (H, W) label map.  Returns the view's render dictionary."""
+        out = render_label_votes(viewpoint_camera, pc, pipe, bg_color, label_map, self.L, acc=self.acc,
+                                 scaling_modifier=scaling_modifier, override_color=override_color)
+        self.views += 1
+        return out
+
+    def seen(self, min_weight: float = 0.0) -> torch.Tensor:
+        """(P,) bool: the Gaussians whose weight total over the views exceeds min_weight."""
+        return self.acc[:, self.L] > min_weight
+
+    def _share(self, column: torch.Tensor) -> torch.Tensor:
+        den = self.acc[:, self.L]
+        return torch.where(den > 0, column / den.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(den))
+
+    def labels(self) -> torch.Tensor:
+        """(P,) int64: the class that holds most of the Gaussian's weight (torch.argmax of the sums), -1 where the Gaussian was
+        never seen - or seen only under labels outside [0, L)."""
+        top, lab = self.acc[:, :self.L].max(dim=1)
+        return torch.where(top > 0, lab, torch.full_like(lab, -1))
+
+    def confidence(self) -> torch.Tensor:
+        """(P,) float32: the winning class's weight over the weight total; 0 where unseen."""
+        return self._share(self.acc[:, :self.L].max(dim=1)[0])
+
+    def ratios(self) -> torch.Tensor:
+        """(P, L): weight on class l over the weight total; 0 where a Gaussian was never seen."""
+        den = self.acc[:, self.L:]
+        return torch.where(den > 0, self.acc[:, :self.L] / den.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(den))
+
+    def select(self, cls: int, threshold: float = 0.5, min_weight: float = 0.0) -> torch.Tensor:
+        """(P,) bool, a `mask` of edit.apply_edit: the seen Gaussians with at least `threshold` of their weight on class `cls` -
+        column `cls` of ratios() >= threshold, formed from that column alone."""
+        if not 0 <= int(cls) < self.L:
+            raise ValueError(f"cls = {cls}: 0 .. {self.L - 1} expected")
+        return (self._share(self.acc[:, int(cls)]) >= threshold) & self.seen(min_weight)
+
+    def label_image(self, ids: torch.Tensor) -> torch.Tensor:
+        """labels()[ids], -1 where ids == -1: the 3D labels seen from the view whose `ids` (the dominant Gaussian per pixel) came
+        from contributions()."""
+        if not torch.is_tensor(ids) or ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError("ids: an int32 or int64 tensor of Gaussian indices expected")
+        lab = self.labels()
+        if self.P == 0:
+            return torch.full(ids.shape, -1, dtype=torch.int64, device=ids.device)
+        return torch.where(ids >= 0, lab[ids.clamp_min(0).long()], torch.full((), -1, dtype=torch.int64, device=ids.device))
+
+
+__all__ = ["MAX_MASKS", "MAX_LABELS", "contributions", "render_contributions", "MaskLifter", "label_votes", "render_label_votes",
+           "LabelLifter"]

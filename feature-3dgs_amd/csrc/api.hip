@@ -385,7 +385,7 @@ CountReadback* count_readback(hipStream_t s, bool may_create) {
 
 extern "C" {
 
-int f3dgs_version(void) { return 31500; }   // 3.15.0 (major * 10000 + minor * 100 + patch): 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
+int f3dgs_version(void) { return 31600; }   // 3.16.0 (major * 10000 + minor * 100 + patch): 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
 
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 
@@ -830,6 +830,36 @@ int f3dgs_contributions(int P, int R, int width, int height, const char* geom_bu
     if (frame_axis_ratio(geom_buffer, &long_axis, &b0, &b1)) { b0 = std::min(std::max(b0, 0), gy); b1 = std::min(std::max(b1, b0), gy); }
     HIP_TRY(launch_contributions(width, height, b0, b1, img.ranges, point_list, geom.rec, img.n_contrib, K, masks, acc, wmax, alpha,
                                  median_depth, ids, id_weight, s));
+    return F3DGS_OK;
+}
+
+int f3dgs_label_votes(int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
+                      const char* image_buffer, const void* labels, int labels_format, int L, float* acc, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: P < 0");
+    if (R < 0 || width <= 0 || height <= 0)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: bad sizes (R = %d, image %d x %d)", R, width, height);
+    if (L < 1 || L > F3DGS_LABEL_VOTES_MAX_LABELS)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: L = %d labels, 1 .. %d are taken", L, F3DGS_LABEL_VOTES_MAX_LABELS);
+    if (labels_format != F3DGS_LABELS_U8 && labels_format != F3DGS_LABELS_I32 && labels_format != F3DGS_LABELS_I64)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: unknown labels format %d", labels_format);
+    if (!labels) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: labels is null");
+    if (!acc) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: acc is null");
+    const uintptr_t elem = labels_format == F3DGS_LABELS_U8 ? 1 : labels_format == F3DGS_LABELS_I32 ? 4 : 8;
+    if (reinterpret_cast<uintptr_t>(labels) % elem)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: labels is off the alignment of its %d-byte element", (int)elem);
+    if (P > 0 && (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)))
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: null state buffer");
+    if (P == 0 || R == 0) return F3DGS_OK;      // nothing blended anywhere: nothing to add
+    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
+    const size_t HW = (size_t)width * height, tiles = (size_t)gx * gy;
+    const GeomState geom = GeomState::carve(const_cast<char*>(geom_buffer), P, nullptr);
+    const ImageState img = ImageState::carve(const_cast<char*>(image_buffer), HW, tiles, nullptr);
+    float long_axis = 0.f;
+    int b0 = 0, b1 = gy;      // the tile rows the forward call listed, as f3dgs_contributions finds them
+    if (frame_axis_ratio(geom_buffer, &long_axis, &b0, &b1)) { b0 = std::min(std::max(b0, 0), gy); b1 = std::min(std::max(b1, b0), gy); }
+    HIP_TRY(launch_label_votes(width, height, b0, b1, img.ranges, BinState::list_of(binning_buffer), geom.rec, img.n_contrib, labels,
+                               labels_format, L, acc, s));
     return F3DGS_OK;
 }
 

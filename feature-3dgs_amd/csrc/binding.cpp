@@ -692,6 +692,20 @@ torch::Tensor MaskUnpack(const torch::Tensor& packed, const c10::optional<torch:
     return out;
 }
 
+// int32 (FH,FW): the largest j whose mask packed[index[j]] has the pixel set, -1 without one (f3dgs_mask_instance_map)
+torch::Tensor MaskInstanceMap(const torch::Tensor& packed, const c10::optional<torch::Tensor>& index, int64_t FH) {
+    check_packed(packed, index, FH, "mask_instance_map");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(packed.device());
+    const int64_t K = index.has_value() ? index->numel() : packed.size(0);
+    torch::Tensor out = torch::empty({FH, packed.size(1)}, packed.options());
+    const int rc = f3dgs_mask_instance_map((int)K, (int)FH, (int)packed.size(1),
+                                           K ? reinterpret_cast<const uint32_t*>(packed.data_ptr()) : nullptr,
+                                           index.has_value() && K ? index->data_ptr<int32_t>() : nullptr, out.data_ptr<int32_t>(),
+                                           current_stream(packed));
+    check_status(rc, "mask_instance_map");
+    return out;
+}
+
 // remove_small_regions of the masks packed[index] (f3dgs_mask_regions).  Returns (words (K,FW,NW) int32, changed (K) bool, area (K)
 // int32, box (K,4) int32, runs): where runs > run_capacity the tensors are unwritten and the caller comes again.
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int64_t>
@@ -816,6 +830,33 @@ Contributions(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffe
         want_pixel ? id_weight->data_ptr<float>() : nullptr, current_stream(imgBuffer));
     check_status(rc, "contributions");
     return std::make_tuple(alpha, median, ids, id_weight);
+}
+
+// the label vote (include/f3dgs.h: f3dgs_label_votes) over the state buffers of a rasterize_gaussians call: labels (H, W) uint8 /
+// int32 / int64; acc (P, L + 1) float32, added to
+void LabelVotes(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imgBuffer, int64_t P,
+                int64_t num_rendered, int64_t H, int64_t W, const torch::Tensor& labels, int64_t L, torch::Tensor& acc) {
+    TORCH_CHECK(imgBuffer.is_cuda() && geomBuffer.is_cuda() && binningBuffer.is_cuda(),
+                "label_votes: the state buffers must live on a HIP device (no CPU path)");
+    TORCH_CHECK(P >= 0 && H > 0 && W > 0 && H * W < (1ll << 31), "label_votes: bad sizes P = ", P, ", image ", H, " x ", W);
+    TORCH_CHECK(L >= 1 && L <= F3DGS_LABEL_VOTES_MAX_LABELS, "label_votes: L = ", L, " labels, 1 .. ", F3DGS_LABEL_VOTES_MAX_LABELS, " are taken");
+    const auto dev = imgBuffer.device();
+    const auto st = labels.scalar_type();
+    TORCH_CHECK(labels.is_cuda() && labels.device() == dev, "label_votes: labels must live on the HIP device of the state buffers (got ",
+                labels.device(), ")");
+    TORCH_CHECK((st == torch::kUInt8 || st == torch::kInt32 || st == torch::kInt64) && labels.is_contiguous() && labels.dim() == 2 &&
+                    labels.size(0) == H && labels.size(1) == W,
+                "label_votes: labels must be contiguous uint8, int32 or int64 (", H, ", ", W, "), got ", st, " ", labels.sizes());
+    TORCH_CHECK(acc.is_cuda() && acc.device() == dev && acc.scalar_type() == torch::kFloat32 && acc.is_contiguous() && acc.dim() == 2 &&
+                    acc.size(0) == P && acc.size(1) == L + 1,
+                "label_votes: acc must be contiguous float32 (", P, ", ", L + 1, ") on the device of the state buffers, got ", acc.sizes());
+    if (P == 0) return;      // a (0, .) tensor has no storage: nothing to add to
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    auto state = [](const torch::Tensor& t) { return t.numel() ? reinterpret_cast<const char*>(t.data_ptr()) : nullptr; };
+    const int format = st == torch::kUInt8 ? F3DGS_LABELS_U8 : st == torch::kInt32 ? F3DGS_LABELS_I32 : F3DGS_LABELS_I64;
+    const int rc = f3dgs_label_votes((int)P, (int)num_rendered, (int)W, (int)H, state(geomBuffer), state(binningBuffer), state(imgBuffer),
+                                     labels.data_ptr(), format, (int)L, acc.data_ptr<float>(), current_stream(imgBuffer));
+    check_status(rc, "label_votes");
 }
 
 // open-vocabulary segmentation (include/f3dgs.h: f3dgs_segment).  feature_map (C,H,W), text (K,Cout) float32; weight (Cout,C) /
@@ -1152,6 +1193,9 @@ PYBIND11_MODULE(_C, m) {
           py::arg("num_rendered"), py::arg("H"), py::arg("W"), py::arg("masks") = py::none(), py::arg("acc") = py::none(),
           py::arg("wmax") = py::none(), py::arg("want_pixel") = true);
     m.attr("CONTRIB_MAX_MASKS") = (int)F3DGS_CONTRIB_MAX_MASKS;
+    m.def("label_votes", &LabelVotes, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imgBuffer"), py::arg("P"),
+          py::arg("num_rendered"), py::arg("H"), py::arg("W"), py::arg("labels"), py::arg("L"), py::arg("acc"));
+    m.attr("LABEL_VOTES_MAX_LABELS") = (int)F3DGS_LABEL_VOTES_MAX_LABELS;
     m.def("feature_pca_moments", &FeaturePcaMoments, py::arg("feature_map"), py::arg("stride"));
     m.def("feature_pca_project", &FeaturePcaProject, py::arg("feature_map"), py::arg("mean"), py::arg("components"),
           py::arg("lo") = py::none(), py::arg("hi") = py::none());
@@ -1185,6 +1229,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("mask_rle_emit", &MaskRleEmit, py::arg("packed"), py::arg("index"), py::arg("FH"), py::arg("lens"), py::arg("ends"), py::arg("out"),
           py::arg("head"));
     m.def("mask_unpack", &MaskUnpack, py::arg("packed"), py::arg("index"), py::arg("FH"));
+    m.def("mask_instance_map", &MaskInstanceMap, py::arg("packed"), py::arg("index"), py::arg("FH"));
     m.def("mask_regions", &MaskRegions, py::arg("packed"), py::arg("index"), py::arg("FH"), py::arg("area_thresh"), py::arg("holes"),
           py::arg("run_capacity"));
     m.attr("BOX_NMS_MAX") = (int)F3DGS_BOX_NMS_MAX;

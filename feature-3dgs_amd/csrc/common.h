@@ -365,6 +365,9 @@ int launch_render_backward(const ViewParams& vp, int C, const uint2* ranges, con
 hipError_t launch_contributions(int W, int H, int band0, int band1, const uint2* ranges, const uint32_t* point_list, const SplatRec* rec,
                                 const uint32_t* n_contrib, int K, const float* masks, float* acc, float* wmax, float* alpha,
                                 float* median_depth, int* ids, float* id_weight, hipStream_t s);
+// contrib.hip: the label vote over the same lists (f3dgs_label_votes): acc (P x (L + 1)) over the one-hot masks of `labels`
+hipError_t launch_label_votes(int W, int H, int band0, int band1, const uint2* ranges, const uint32_t* point_list, const SplatRec* rec,
+                              const uint32_t* n_contrib, const void* labels, int format, int L, float* acc, hipStream_t s);
 struct BwdArgs;
 void launch_render_backward_pl(BwdArgs a, int C, hipStream_t s);     // render_bwd_pl.hip
 void launch_tile_order(const uint32_t* tile_len, size_t tiles, uint32_t* order, uint32_t band_b0, uint32_t band_tb, hipStream_t s);

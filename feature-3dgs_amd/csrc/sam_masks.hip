@@ -446,6 +446,45 @@ __global__ void __launch_bounds__(256) unpack_kernel(size_t total, int FH, int F
     }
 }
 
+// The painter's picture of K masks (show_anns): per pixel the largest j whose mask has the bit set, -1 without one.  A workgroup
+// takes IM_COLS columns x IM_WORDS words of a column (32 rows each); a thread owns one word position, walks the masks from the
+// last one down, four words in flight, and paints each bit the first time it meets it into the LDS tile, which is then stored
+// by rows.  The words of a column are consecutive (IM_WORDS x 4 bytes per column and mask are read together), the stores are
+// rows of IM_COLS x 4 bytes.
+constexpr int IM_COLS = 32, IM_WORDS = 8, IM_ROWS = 32 * IM_WORDS, IM_PITCH = IM_COLS + 1;
+
+__global__ void __launch_bounds__(256) instance_map_kernel(int K, int FH, int FW, int NW, int tiles_x, const uint32_t* __restrict__ packed,
+                                                           const int32_t* __restrict__ index, int32_t* __restrict__ out) {
+    __shared__ int32_t tile[IM_ROWS * IM_PITCH];
+    const int x0 = (int)(blockIdx.x % tiles_x) * IM_COLS, w0 = (int)(blockIdx.x / tiles_x) * IM_WORDS;
+    const int wl = threadIdx.x % IM_WORDS, xl = threadIdx.x / IM_WORDS;
+    const int x = x0 + xl, wy = w0 + wl;
+    int32_t* const mine = tile + (wl * 32) * IM_PITCH + xl;           // bit b of this thread's word: mine[b * IM_PITCH]
+#pragma unroll
+    for (int b = 0; b < 32; b++) mine[b * IM_PITCH] = -1;
+    if (x < FW && wy < NW) {
+        const size_t at = (size_t)x * NW + wy;
+        uint32_t open = ~0u;                                          // bits no mask has painted yet
+        auto paint = [&](uint32_t w, int j) {
+            for (uint32_t t = w & open; t; t &= t - 1u) mine[(int)__builtin_ctz(t) * IM_PITCH] = j;
+            open &= ~w;
+        };
+        int j = K - 1;
+        for (; j >= 3 && open; j -= 4) {
+            const uint32_t a = mask_of(packed, index, j, FW, NW)[at], b = mask_of(packed, index, j - 1, FW, NW)[at];
+            const uint32_t c = mask_of(packed, index, j - 2, FW, NW)[at], d = mask_of(packed, index, j - 3, FW, NW)[at];
+            paint(a, j); paint(b, j - 1); paint(c, j - 2); paint(d, j - 3);
+        }
+        for (; j >= 0 && open; j--) paint(mask_of(packed, index, j, FW, NW)[at], j);
+    }
+    __syncthreads();
+    const int cx = threadIdx.x % IM_COLS;
+    for (int r = threadIdx.x / IM_COLS; r < IM_ROWS; r += 256 / IM_COLS) {
+        const int y = w0 * 32 + r;
+        if (y < FH && x0 + cx < FW) out[(size_t)y * FW + x0 + cx] = tile[r * IM_PITCH + cx];
+    }
+}
+
 int check_geometry(const char* who, int M, int h, int w, int S, int ih, int iw, int H, int W) {
     if (M < 0 || h < 1 || w < 1 || S < 1 || ih < 1 || iw < 1 || H < 1 || W < 1)
         return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: bad sizes M=%d h=%d w=%d S=%d input=%dx%d original=%dx%d", who, M, h, w, S, ih, iw, H, W);
@@ -579,6 +618,15 @@ int f3dgs_mask_unpack(int K, int FH, int FW, const uint32_t* packed, const int32
     const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 32);
     hipLaunchKernelGGL(unpack_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), total, FH, FW, (FH + 31) / 32, packed, index, out);
     return last_launch("mask_unpack");
+}
+
+int f3dgs_mask_instance_map(int K, int FH, int FW, const uint32_t* packed, const int32_t* index, int32_t* out, void* stream) {
+    if (const int rc = check_packed("mask_instance_map", K, FH, FW)) return rc;
+    if (!out || (K > 0 && !packed)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "mask_instance_map: null pointer");
+    const int NW = (FH + 31) / 32, tiles_x = (FW + IM_COLS - 1) / IM_COLS, tiles_y = (NW + IM_WORDS - 1) / IM_WORDS;
+    hipLaunchKernelGGL(instance_map_kernel, dim3(tiles_x * tiles_y), dim3(256), 0, static_cast<hipStream_t>(stream), K, FH, FW, NW, tiles_x,
+                       packed, index, out);
+    return last_launch("mask_instance_map");
 }
 
 }  // extern "C"

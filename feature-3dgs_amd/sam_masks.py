@@ -16,12 +16,13 @@ Replaces what the reference runs after the decoder (encoders/sam_encoder/segment
     masks = upscale_masks(low_res, 1024, (576, 1024), (1080, 1920))              # the drop-in for postprocess_masks
     keep, count = box_nms(boxes, scores, 0.7);  keep = batched_nms(boxes, scores, idxs, 0.7)
     rles = masks_to_rle(st.packed, st.kept_index[:k]);  dense = unpack_masks(st.packed, index)
+    ids = instance_map(st.packed, paint_order(st.area))                          # segment.py:57-70 show_anns: int32 (FH, FW), -1 = none
     new, changed = remove_small_regions(st.packed, 100, "holes", index)          # utils/amg.py:remove_small_regions, K masks at once
     sr = postprocess_small_regions(st.packed, 100, index)                        # holes, then islands: packed, changed, area, box
     pp = MaskPostprocessor((1080, 1920), min_mask_region_area=100);  pp.add_batch(...);  records = pp.finish()      # generate's records
 
 csrc/sam_masks.hip and csrc/mask_regions.hip behind include/f3dgs.h (f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms,
-f3dgs_mask_rle_*, f3dgs_mask_unpack, f3dgs_mask_regions).  The small-region removal labels the bit-packed masks where they lie:
+f3dgs_mask_rle_*, f3dgs_mask_unpack, f3dgs_mask_instance_map, f3dgs_mask_regions).  The small-region removal labels the bit-packed masks where they lie:
 its nodes are the vertical runs of a column, joined by a union-find of integer atomics; no dense label image, no OpenCV.
 Both resizes are PyTorch's upsample_bilinear2d (align_corners=False) in fp32, one rounding per operation, kept as two stages;
 counts, boxes and bits are integers, the stability score one IEEE division: two calls give the same bits.  The networks (image
@@ -275,6 +276,26 @@ def unpack_masks(packed, index=None) -> torch.Tensor:
     """bool (K,FH,FW) of the masks packed[index] (all, without index)."""
     w, index, FH, FW = _packed_args(packed, index, "the masks are unpacked")
     return _C().mask_unpack(w, index, FH)
+
+
+@torch.no_grad()
+def instance_map(packed, index=None) -> torch.Tensor:
+    """The painter's picture of the masks packed[index] (all, without index), what the reference's show_anns
+    (encoders/sam_encoder/segment.py:57-70) paints: int32 (FH,FW), per pixel the LARGEST j whose mask index[j] covers it - later
+    masks paint over earlier ones -, -1 where none does.  Rows may repeat in index.  With index = paint_order(areas) the small
+    masks lie on top, as in show_anns; the values are positions in `index`.  One launch, no host read; the map is a label map
+    contrib.label_votes takes as it is."""
+    w, index, FH, FW = _packed_args(packed, index, "the instance map is painted")
+    return _C().mask_instance_map(w, index, FH)
+
+
+def paint_order(areas) -> torch.Tensor:
+    """The order show_anns paints in: sorted(range(K), key=area, reverse=True) - descending areas, equal areas in their
+    former order (Python's sort is stable, with reverse too).  int64 (K,), on the device of `areas` if it is a tensor."""
+    a = torch.as_tensor(areas)
+    if a.dim() != 1 or a.dtype == torch.bool:
+        raise ValueError(f"areas: K numbers expected, got {a.dtype} {tuple(a.shape)}")
+    return torch.sort(a.detach(), descending=True, stable=True)[1]
 
 
 # ---- small regions ----------------------------------------------------------------------------------------------------------

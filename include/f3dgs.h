@@ -473,6 +473,24 @@ int f3dgs_contributions(int P, int R, int width, int height,
                         void* stream /* hipStream_t */);
 
 /*
+ * The label vote: f3dgs_contributions' `acc` over the one-hot masks of an integer label map, for any number of labels, in ONE
+ * walk - a pixel has one label, so the (L, H, W) mask stack is never formed and the lists are not walked once per seven masks.
+ * `labels` is H x W in the format F3DGS_LABELS_U8, _I32 or _I64 (below; what f3dgs_segment writes is _I64), aligned to its
+ * element.  The weights w are those of f3dgs_contributions (the forward's, bit for bit).  With l = labels[p]: if 0 <= l < L -
+ * compared on the full-width value - acc[g][l] += w; in every case acc[g][L] += w: a label outside [0, L) belongs to no class
+ * but counts in the weight total.  acc: (P, L + 1) floats, ADDED TO (zeroed once by the caller, accumulated over many views),
+ * indexed in size_t; float atomics in a varying order, as for f3dgs_contributions.  1 <= L <= F3DGS_LABEL_VOTES_MAX_LABELS.
+ * F3DGS_ERR_INVALID_ARGUMENT, before any device work: P < 0, a bad size, L out of range, an unknown format, a NULL or
+ * misaligned labels, a NULL acc, a null state buffer while P > 0 (binning_buffer may be NULL when R == 0).  P == 0 or R == 0:
+ * returns F3DGS_OK without touching the device.  No scratch, no host read, no memset; one launch on `stream`: capturable.
+ */
+#define F3DGS_LABEL_VOTES_MAX_LABELS 65536
+int f3dgs_label_votes(int P, int R, int width, int height,
+                      const char* geom_buffer, const char* binning_buffer, const char* image_buffer,
+                      const void* labels /* H x W */, int labels_format /* F3DGS_LABELS_U8 | _I32 | _I64 */, int L,
+                      float* acc /* P x (L + 1), ADDED TO */, void* stream /* hipStream_t */);
+
+/*
  * Forward-only counterpart (the inference side, render.py:169-171, :137-139, :294-296): the rendered feature map (C,H,W)
  * is resized (bilinear, align_corners=True) to (Hg,Wg) and - if weight / bias are given - decoded by the 1x1 conv into
  * `out` (Cout,Hg,Wg), fp32 or (out_is_half != 0) IEEE fp16 as render.py stores it.  Without a decoder Cout must equal C.
@@ -612,6 +630,11 @@ int f3dgs_seg_colorize(int N, int H, int W, int L, const void* labels, int label
  * of mask k to out[ends[k] - lens[k] ..) where they end within `capacity` entries (a mask that does not fit is left out whole:
  * the caller compares ends[K - 1] with capacity).  f3dgs_mask_unpack: K x FH x FW bytes 0 / 1.  One launch each.
  *
+ * f3dgs_mask_instance_map: the painter's picture of K packed masks (encoders/sam_encoder/segment.py:57-70 show_anns, which
+ * paints the masks in the caller's order, later over earlier): out[y][x] (FH x FW int32, row-major) is the largest j < K whose
+ * mask index[j] (mask j without an index; rows may repeat) has bit (x, y) set, -1 where none has.  K == 0 writes all -1 (packed
+ * may then be NULL).  One launch, no host read.  F3DGS_ERR_INVALID_ARGUMENT: bad sizes, a NULL out, a NULL packed with K > 0.
+ *
  * f3dgs_mask_regions: utils/amg.py remove_small_regions (automatic_mask_generator.py:325-373 calls it twice per mask) of K packed
  * masks (`index` as above; `packed` is only read).  `holes` != 0 labels the background (clear bits of rows < FH), 0 the foreground,
  * with 8-connectivity; a component is small when its area < area_thresh (strict, a double).  `changed`[k] = 1 iff mask k has a
@@ -649,6 +672,8 @@ int f3dgs_mask_rle_emit(int K, int FH, int FW, const uint32_t* packed, const int
                         const int64_t* ends, int64_t capacity, int32_t* out, void* stream /* hipStream_t */);
 int f3dgs_mask_unpack(int K, int FH, int FW, const uint32_t* packed, const int32_t* index /* or NULL */, unsigned char* out,
                       void* stream /* hipStream_t */);
+int f3dgs_mask_instance_map(int K, int FH, int FW, const uint32_t* packed, const int32_t* index /* or NULL */,
+                            int32_t* out /* FH x FW, row-major */, void* stream /* hipStream_t */);
 size_t f3dgs_mask_regions_scratch_bytes(int K, int FW, int64_t run_capacity);
 int f3dgs_mask_regions(int K, int FH, int FW, const uint32_t* packed, const int32_t* index /* or NULL */, int holes, double area_thresh,
                        int64_t run_capacity, uint32_t* out, unsigned char* changed, int32_t* area, int32_t* box /* K x 4 */,
