@@ -573,15 +573,19 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
     const TotalsJob tj = {geom.ref_partial, (P + 255) / 256, geom.counters, rb.dev, capturing ? nullptr : rb.done};
     const OffsetSumsJob sums = {geom.tiles_touched, geom.scan_tmp, geom.scan_sub};
     bool sums_done = false;         // small scenes: the one-workgroup depth sort leaves the list-offset sums as well
+    bool counts_in_a = false;       // the multi-launch depth sort leaves the tile counts in depth order in key_a (GeomState::key_a)
     if (onesweep) launch_depth_sort_onesweep(geom, (size_t)P, s);
-    else HIP_TRY(launch_depth_sort(geom.depth_key, geom.key_a, geom.val_a, geom.key_b, geom.val_b, (size_t)P, geom.hist, &tj, s, &sums, &sums_done));
+    else HIP_TRY(launch_depth_sort(geom.depth_key, geom.key_a, geom.val_a, geom.key_b, geom.val_b, (size_t)P, geom.hist, &tj, s, &sums, &sums_done, &counts_in_a));
     if ((rc = check_debug(debug, s, "depth sort"))) return rc;
     tm.mark("depth_sort");
     const uint32_t* order = geom.val_a;
+    const uint32_t* counts_in_order = counts_in_a ? geom.key_a : nullptr;
 
     // instance offsets in depth order (three-kernel flavour only; the single-pass emit scans on the fly)
-    if (!onesweep && !sums_done)
-        launch_offset_sums(geom.tiles_touched, order, (size_t)P, geom.scan_tmp, geom.scan_sub, s);
+    if (!onesweep && !sums_done) {
+        if (counts_in_order) launch_offset_sums(counts_in_order, nullptr, (size_t)P, geom.scan_tmp, geom.scan_sub, s);
+        else launch_offset_sums(geom.tiles_touched, order, (size_t)P, geom.scan_tmp, geom.scan_sub, s);
+    }
 
     // [0] instances in our lists, [1] the reference's bounding-rectangle count,
     // [2] != 0: a visible Gaussian of the frame is longer than bwd_bf16_max_ratio times its width (the single-pass flavour of the
@@ -615,7 +619,7 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
     tm.mark("scan+sync");
 
     const int bits = tile_bits((int)tiles);
-    const int passes = (bits + RADIX_BITS - 1) / RADIX_BITS;
+    const int passes = (bits + RADIX_BITS - 1) / RADIX_BITS;        // (of either flavour: tile_digit_split keeps the count of 8-bit digits)
     BinState bin;
     for (;;) {
         const uint32_t n_carve = known ? N : cap;           // entries the binning buffer holds in this round
@@ -643,7 +647,7 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
         } else {
             // presets the ranges too; a captured frame that finds no room raises the slot's sticky word (the host of an eager frame
             // learns it from the count)
-            launch_emit_instances(P, geom, order, vp.gx, vp.gy, band, cull, in_tile, in_id, bin.ranges_enc, img.tile_len, n_carve,
+            launch_emit_instances(P, geom, order, counts_in_order, vp.gx, vp.gy, band, cull, in_tile, in_id, bin.ranges_enc, img.tile_len, n_carve,
                                   known ? nullptr : geom.counters, capturing ? rb.dev + 4 : nullptr, s);
             if ((rc = check_debug(debug, s, "emit"))) return rc;
             tm.mark("emit");

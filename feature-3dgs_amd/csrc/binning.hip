@@ -8,12 +8,14 @@
 //   1. stable sort of the P Gaussians by their 32-bit depth key (4 passes over P pairs);
 //   2. prefix-sum of tiles_touched taken IN DEPTH ORDER;
 //   3. emit instances (tile, id) in depth order;
-//   4. stable sort of the N instances by tile id only (2 passes at <= 65536 tiles).
+//   4. stable sort of the N instances by tile id only (2 passes at <= 65536 tiles, digits as wide as the tile count needs).
+// The last pass of 1 leaves every Gaussian's tile count at its place in the depth order (nobody reads that pass's keys), so 2 and
+// 3 read the counts in a row.
 // An LSD radix sort is "sort by low key, then stably by high key": steps 1+4 are exactly the
 // reference's sort on (tile | depth) with ties broken by ascending Gaussian id, because the depth
 // sort starts from id order and both sorts are stable (Q6 in SURVEY.md section 8a).
 //
-// Radix pass = 3 launches: per-workgroup digit histogram, per-digit row scan (grid = 256),
+// Radix pass = 3 launches: per-workgroup digit histogram, per-digit row scan (grid = digits),
 // stable scatter (wave-level match with ballots, wave-ordered LDS counters).
 
 #include <atomic>
@@ -107,26 +109,61 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_hist_kernel(const uint32_t
     // last item write their zero column of the histogram matrix and nothing else.  A count above the capacity reads as ZERO: the
     // emit kernel stored nothing for such a frame (the arrays hold what the allocator left there), the tile ranges stay empty
     if (n_dev) { const size_t nd = *n_dev; n = nd <= n ? nd : 0; }     // (a frame that does not fit is void: nothing was emitted)
-    if (tj.partial && blockIdx.x == 0) run_totals_job<SORT_THREADS>(tj);
-    for (int d = threadIdx.x; d < BINS; d += SORT_THREADS) h[d] = 0;
-    __syncthreads();
+    // every key of the thread is requested before anything else, as in the scatter kernel: written as load-and-count per item,
+    // the compiled loop waited for each key in front of its LDS atomic - ITEMS memory round trips one behind the other
     const size_t base = (size_t)blockIdx.x * CHUNK;
+    uint32_t key[ITEMS];
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
         const size_t i = base + (size_t)k * SORT_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&h[(keys[i] >> shift) & (BINS - 1)], 1u);
+        key[k] = i < n ? keys[i] : 0u;
+    }
+    if (tj.partial && blockIdx.x == 0) run_totals_job<SORT_THREADS>(tj);
+    for (int d = threadIdx.x; d < BINS; d += SORT_THREADS) h[d] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < ITEMS; k++) {
+        const size_t i = base + (size_t)k * SORT_THREADS + threadIdx.x;
+        if (i < n) atomicAdd(&h[(key[k] >> shift) & (BINS - 1)], 1u);
     }
     __syncthreads();
     for (int d = threadIdx.x; d < BINS; d += SORT_THREADS) hist[(size_t)d * nb + blockIdx.x] = h[d];  // digit-major
 }
 
 // One workgroup per digit: exclusive scan of that digit's per-workgroup counts, total to totals[d].
+// The first ROWSCAN_GROUPS x 256 columns (c3: the whole row, 489 / 1289 columns) are requested at once and scanned behind ONE
+// barrier - wave scans in registers, the 4 x ROWSCAN_GROUPS wave totals through LDS; a loop of load, scan (two barriers), store
+// per 256 columns was as many memory round trips one behind the other.  Longer rows (c5) go on in that loop.
+constexpr int ROWSCAN_GROUPS = 8;
 __global__ void __launch_bounds__(256) radix_rowscan_kernel(uint32_t* __restrict__ hist, uint32_t nb,
                                                             uint32_t* __restrict__ totals) {
     __shared__ uint32_t sh[8];
+    __shared__ uint4 wtot[ROWSCAN_GROUPS];        // [group] = totals of its four waves
     uint32_t* row = hist + (size_t)blockIdx.x * nb;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t v[ROWSCAN_GROUPS], inc[ROWSCAN_GROUPS];
+#pragma unroll
+    for (int k = 0; k < ROWSCAN_GROUPS; k++) {
+        const uint32_t i = (uint32_t)k * 256 + threadIdx.x;
+        const uint32_t r = row[i < nb ? i : 0u];        // (unconditional loads: one run of requests, one wait)
+        v[k] = i < nb ? r : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < ROWSCAN_GROUPS; k++) {
+        inc[k] = (uint32_t)k * 256 < nb ? wave_incl_scan(v[k], lane) : 0u;       // (uniform: groups behind the row are zero)
+        if (lane == 63) (&wtot[k].x)[w] = inc[k];
+    }
+    __syncthreads();
     uint32_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += 256) {
+#pragma unroll
+    for (int k = 0; k < ROWSCAN_GROUPS; k++) {
+        const uint4 t = wtot[k];
+        const uint32_t before = carry + (w > 0 ? t.x : 0u) + (w > 1 ? t.y : 0u) + (w > 2 ? t.z : 0u);
+        const uint32_t i = (uint32_t)k * 256 + threadIdx.x;
+        if (i < nb) row[i] = before + inc[k] - v[k];
+        carry += t.x + t.y + t.z + t.w;
+    }
+    for (uint32_t base = ROWSCAN_GROUPS * 256; base < nb; base += 256) {
         const uint32_t i = base + threadIdx.x;
         const uint32_t v = i < nb ? row[i] : 0;
         uint32_t tot;
@@ -147,15 +184,21 @@ __device__ __forceinline__ void record_range(uint2* ranges_enc, uint32_t tile, b
     if (last) atomicMin(&ranges_enc[tile].y, 0xFFFFFFFFu - (pos + 1u));
 }
 
-template <int BITS, int ITEMS, bool REORDER, bool RANGES>
+// COUNTS (final pass of the depth sort): nobody reads that pass's sorted keys, so an item's slot of keys_out receives
+// payload[value] instead - the Gaussian's tile count at its place in the depth order (GeomState::key_a), gathered here, where
+// the id is in a register anyway, rather than by the two kernels that walk the order afterwards.  The same stores, no more LDS.
+template <int BITS, int ITEMS, bool REORDER, bool RANGES, bool COUNTS = false>
 __global__ void __launch_bounds__(SORT_THREADS)
 radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                      uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out, size_t n, int shift,
                      uint32_t nb, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ totals,
-                     uint2* __restrict__ ranges_enc, const uint32_t* __restrict__ n_dev) {
+                     uint2* __restrict__ ranges_enc, const uint32_t* __restrict__ n_dev,
+                     const uint32_t* __restrict__ payload) {
     constexpr int BINS = 1 << BITS;
     constexpr int CHUNK = SORT_THREADS * ITEMS;
-    constexpr int BPT = BINS / SORT_THREADS;   // bins per thread in the offset phase
+    // bins per thread in the offset phase; fewer bins than threads (digits of 4 ... 7 bits): the first BINS threads own one each
+    constexpr int BPT = BINS >= SORT_THREADS ? BINS / SORT_THREADS : 1;
+    static_assert(BINS >= SORT_THREADS ? BINS % SORT_THREADS == 0 : true, "whole bins per thread");
     if (n_dev) {        // (see radix_hist_kernel) a launch sized by a capacity: the workgroups behind the last item have nothing to move
         const size_t nd = *n_dev;
         n = nd <= n ? nd : 0;
@@ -176,16 +219,17 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
 
     const size_t wbase = (size_t)blockIdx.x * CHUNK + (size_t)w * (ITEMS * 64);
     uint32_t key[ITEMS];
-    uint32_t val[REORDER ? ITEMS : 1];
+    constexpr bool VAL_FIRST = REORDER || COUNTS;
+    uint32_t val[VAL_FIRST ? ITEMS : 1];
     uint32_t rank[ITEMS];
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    // every request of the chunk goes out first (the values are only needed by the LDS reorder: their latency hides
-    // behind the ranking)
+    // every request of the chunk goes out first (the values are only needed by the LDS reorder - and by the gather of COUNTS:
+    // their latency hides behind the ranking)
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
         const size_t i = wbase + (size_t)k * 64 + lane;
         key[k] = i < n ? keys_in[i] : 0xFFFFFFFFu;
-        if constexpr (REORDER) val[k] = (vals_in && i < n) ? vals_in[i] : (uint32_t)i;
+        if constexpr (VAL_FIRST) val[k] = (vals_in && i < n) ? vals_in[i] : (uint32_t)i;
     }
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
@@ -208,16 +252,29 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
         if (valid && before == 0) vcnt[w * BINS + d] = old + (uint32_t)__popcll(peers);
         rank[k] = old + before;
     }
+    // COUNTS without the LDS reorder: a lane stores its own items, so their payloads are requested here, one more register per
+    // item, and arrive behind the offset phase
+    uint32_t pay[(COUNTS && !REORDER) ? ITEMS : 1];
+    (void)pay;
+    if constexpr (COUNTS && !REORDER) {
+#pragma unroll
+        for (int k = 0; k < ITEMS; k++) {
+            const size_t i = wbase + (size_t)k * 64 + lane;
+            pay[k] = payload[i < n ? val[k] : 0u];      // (unconditional: one run of loads, one wait)
+        }
+    }
     __syncthreads();
-    // thread t owns digits [t*BPT, (t+1)*BPT): turn per-wave counts into offsets
+    // thread t owns digits [t*BPT, (t+1)*BPT) - where there are fewer digits than threads, digit t or none: turn per-wave
+    // counts into offsets (every thread takes part in the scans)
     {
         uint32_t tot[BPT], run = 0, blk[BPT], brun = 0;
 #pragma unroll
         for (int q = 0; q < BPT; q++) {
             const uint32_t d = threadIdx.x * BPT + q;
-            tot[q] = totals[d];
+            const bool own = BINS >= SORT_THREADS || d < (uint32_t)BINS;
+            tot[q] = own ? totals[d] : 0u;
             run += tot[q];
-            blk[q] = cnt[0][d] + cnt[1][d] + cnt[2][d] + cnt[3][d];
+            blk[q] = own ? cnt[0][d] + cnt[1][d] + cnt[2][d] + cnt[3][d] : 0u;
             brun += blk[q];
         }
         uint32_t digit_base = block_excl_scan_256(run, sh, nullptr);
@@ -225,6 +282,7 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
 #pragma unroll
         for (int q = 0; q < BPT; q++) {
             const uint32_t d = threadIdx.x * BPT + q;
+            if (BINS < SORT_THREADS && d >= (uint32_t)BINS) break;
             const uint32_t g = digit_base + hist[(size_t)d * nb + blockIdx.x];
             if (REORDER) { gbase[d] = g; lstart[d] = local_base; }
             uint32_t r2 = REORDER ? local_base : g;
@@ -253,16 +311,45 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
         __syncthreads();
         const size_t cbase = (size_t)blockIdx.x * CHUNK;
         const uint32_t have = (uint32_t)min((size_t)CHUNK, n - cbase);
+        if constexpr (COUNTS) {
+            // the ids come out of the LDS image in their new order: all of a thread's gathers go out before its first store (one
+            // memory latency for the ITEMS of them), and nothing is staged through LDS.  (Gathered before the ranking and staged
+            // through 8 KB more of LDS instead, the c3 pass took 13.9 us against 14.4: inside the run-to-run spread.  Either way the
+            // pass is 6 us longer than one that stores keys - a million 4-byte reads all over a 4 MB table cost that wherever
+            // they are issued; scan_reduce_kernel is 6 us shorter without them, and the emit kernel 7 us.)
+            static_assert(!RANGES, "the depth sort records no ranges");
+            // (the gathers are unconditional - a slot behind the chunk's items reads item 0's, the chunk holds one at least - so
+            // that they compile to one straight run of loads with a single wait in front of the stores)
+            uint32_t pos[ITEMS], id[ITEMS], c[ITEMS];
 #pragma unroll
-        for (int k = 0; k < ITEMS; k++) {
-            const uint32_t j = (uint32_t)k * SORT_THREADS + threadIdx.x;
-            if (j < have) {
-                const uint32_t kk = skey[j];
-                const uint32_t d = (kk >> shift) & (BINS - 1);
-                const uint32_t pos = gbase[d] + (j - lstart[d]);
-                keys_out[pos] = kk;
-                vals_out[pos] = sval[j];
-                if (RANGES) record_range(ranges_enc, kk, j == 0 || skey[j - 1] != kk, j + 1 == have || skey[j + 1] != kk, pos);
+            for (int k = 0; k < ITEMS; k++) {
+                const uint32_t j = (uint32_t)k * SORT_THREADS + threadIdx.x;
+                const uint32_t jj = j < have ? j : 0u;
+                const uint32_t d = (skey[jj] >> shift) & (BINS - 1);
+                pos[k] = gbase[d] + (jj - lstart[d]);
+                id[k] = sval[jj];
+                c[k] = payload[id[k]];
+            }
+#pragma unroll
+            for (int k = 0; k < ITEMS; k++) {
+                const uint32_t j = (uint32_t)k * SORT_THREADS + threadIdx.x;
+                if (j < have) {
+                    keys_out[pos[k]] = c[k];
+                    vals_out[pos[k]] = id[k];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < ITEMS; k++) {
+                const uint32_t j = (uint32_t)k * SORT_THREADS + threadIdx.x;
+                if (j < have) {
+                    const uint32_t kk = skey[j];
+                    const uint32_t d = (kk >> shift) & (BINS - 1);
+                    const uint32_t pos = gbase[d] + (j - lstart[d]);
+                    keys_out[pos] = kk;
+                    vals_out[pos] = sval[j];
+                    if (RANGES) record_range(ranges_enc, kk, j == 0 || skey[j - 1] != kk, j + 1 == have || skey[j + 1] != kk, pos);
+                }
             }
         }
     } else {
@@ -272,8 +359,13 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
             if (i < n) {
                 const uint32_t d = (key[k] >> shift) & (BINS - 1);
                 const uint32_t pos = cnt[w][d] + rank[k];
-                keys_out[pos] = key[k];
-                vals_out[pos] = vals_in ? vals_in[i] : (uint32_t)i;
+                if constexpr (COUNTS) {
+                    keys_out[pos] = pay[k];
+                    vals_out[pos] = val[k];
+                } else {
+                    keys_out[pos] = key[k];
+                    vals_out[pos] = vals_in ? vals_in[i] : (uint32_t)i;
+                }
             }
         }
     }
@@ -622,7 +714,8 @@ bool small_sort_usable() {
 template <int BITS, int ITEMS>
 static hipError_t radix_pass(const uint32_t* ki, const uint32_t* vi, uint32_t* ko, uint32_t* vo, size_t n, int shift,
                              uint32_t* hist, hipStream_t s, uint2* ranges_enc = nullptr, const TotalsJob* tj = nullptr,
-                             const uint32_t* n_dev = nullptr) {
+                             const uint32_t* n_dev = nullptr, const uint32_t* payload = nullptr) {
+    // `payload` (the depth sort's final pass): ko receives payload[value] instead of the key (radix_scatter_kernel, COUNTS)
     hipError_t rc = hipSuccess;
     constexpr int BINS = 1 << BITS;
     static_assert(ITEMS >= SORT_ITEMS, "the histogram buffers are sized for SORT_ITEMS keys per thread");
@@ -632,13 +725,33 @@ static hipError_t radix_pass(const uint32_t* ki, const uint32_t* vi, uint32_t* k
                        tj ? *tj : TotalsJob{nullptr, 0, nullptr, nullptr}, n_dev);
     if (tj && tj->ready) rc = hipEventRecord(tj->ready, s);        // the totals are final behind this launch
     hipLaunchKernelGGL(radix_rowscan_kernel, dim3(BINS), dim3(256), 0, s, hist, nb, totals);
+    const uint32_t* const no_payload = nullptr;
+    if constexpr (ITEMS == SORT_ITEMS && (BITS == RADIX_BITS || BITS == DEPTH_RADIX_BITS)) {        // the depth sort's shapes
+        if (payload) {
+            hipLaunchKernelGGL((radix_scatter_kernel<BITS, ITEMS, (BITS <= 8), false, true>), dim3(nb), dim3(SORT_THREADS), 0, s, ki,
+                               vi, ko, vo, n, shift, nb, hist, totals, (uint2*)nullptr, n_dev, payload);
+            return rc;
+        }
+    }
     if (ranges_enc && BITS <= 8)
         hipLaunchKernelGGL((radix_scatter_kernel<BITS, ITEMS, true, true>), dim3(nb), dim3(SORT_THREADS), 0, s, ki, vi, ko, vo, n,
-                           shift, nb, hist, totals, ranges_enc, n_dev);
+                           shift, nb, hist, totals, ranges_enc, n_dev, no_payload);
     else
         hipLaunchKernelGGL((radix_scatter_kernel<BITS, ITEMS, (BITS <= 8), false>), dim3(nb), dim3(SORT_THREADS), 0, s, ki, vi, ko,
-                           vo, n, shift, nb, hist, totals, (uint2*)nullptr, n_dev);
+                           vo, n, shift, nb, hist, totals, (uint2*)nullptr, n_dev, no_payload);
     return rc;
+}
+
+// A tile-sort pass of `bits` bits (tile_digit_split: 4 ... 8; a single pass of fewer bits ranks 4, the upper ones are zero)
+static void tile_radix_pass(int bits, const uint32_t* ki, const uint32_t* vi, uint32_t* ko, uint32_t* vo, size_t n, int shift,
+                            uint32_t* hist, hipStream_t s, uint2* ranges_enc, const uint32_t* n_dev) {
+    switch (bits) {
+        case 8: (void)radix_pass<8, 16>(ki, vi, ko, vo, n, shift, hist, s, ranges_enc, nullptr, n_dev); break;
+        case 7: (void)radix_pass<7, 16>(ki, vi, ko, vo, n, shift, hist, s, ranges_enc, nullptr, n_dev); break;
+        case 6: (void)radix_pass<6, 16>(ki, vi, ko, vo, n, shift, hist, s, ranges_enc, nullptr, n_dev); break;
+        case 5: (void)radix_pass<5, 16>(ki, vi, ko, vo, n, shift, hist, s, ranges_enc, nullptr, n_dev); break;
+        default: (void)radix_pass<4, 16>(ki, vi, ko, vo, n, shift, hist, s, ranges_enc, nullptr, n_dev); break;
+    }
 }
 
 void launch_radix_sort_pairs(uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, uint32_t* val_b, size_t n, int nbits,
@@ -664,21 +777,27 @@ void launch_radix_sort_pairs(uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, 
                                (uint32_t)n, passes, none, (uint2*)nullptr, n_dev, OffsetSumsJob{nullptr, nullptr, nullptr});
         return;
     }
+    // the multi-launch passes: the same number of them, digits as wide as the key needs (tile_digit_split, common.h); the one-launch
+    // sort above keeps its 8-bit steps
+    const DigitSplit split = tile_digit_split(nbits);
     for (int p = 0; p < passes; p++) {
         uint32_t* ki = in_a ? key_a : key_b;
         uint32_t* vi = in_a ? val_a : val_b;
         uint32_t* ko = in_a ? key_b : key_a;
         uint32_t* vo = in_a ? val_b : val_a;
-        (void)radix_pass<RADIX_BITS, 16>(ki, vi, ko, vo, n, p * RADIX_BITS, hist, s, p == passes - 1 ? ranges_enc : nullptr, nullptr, n_dev);
+        tile_radix_pass(split.width[p], ki, vi, ko, vo, n, split.shift[p], hist, s, p == passes - 1 ? ranges_enc : nullptr, n_dev);
         in_a = !in_a;
     }
 }
 
 // Depth sort of the Gaussians: 32-bit keys in `keys` (read-only), values = indices.  Three passes of 11/11/10
-// bits; the sorted ids end in val_a (and the sorted keys in key_a).
+// bits; the sorted ids end in val_a, and in key_a the sorted keys - or, given `counts_in_a`, what the frame reads next in that
+// order: the tile counts (common.h).
 hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, uint32_t* val_b, size_t n,
-                             uint32_t* hist, const TotalsJob* tj, hipStream_t s, const OffsetSumsJob* sums, bool* sums_done) {
+                             uint32_t* hist, const TotalsJob* tj, hipStream_t s, const OffsetSumsJob* sums, bool* sums_done,
+                             bool* counts_in_a) {
     if (sums_done) *sums_done = false;
+    if (counts_in_a) *counts_in_a = false;
     if (n == 0) return hipSuccess;
     if (n <= (size_t)SMALL_SORT_MAX && small_sort_usable<false>()) {
         // the totals the host waits for go out in a launch of their own, in FRONT of the sort: behind it the host would sit out the
@@ -697,6 +816,8 @@ hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* va
         if (sums && sums_done) *sums_done = true;
         return rc;
     }
+    // the last pass hands the tile counts on in the new order instead of the keys, where the caller can take them
+    const uint32_t* const payload = (counts_in_a && sums) ? sums->tiles_touched : nullptr;
     if (n > 200000) {
         // large P: four 8-bit passes are faster than three 11-bit ones (measured at 1M: 0.105 vs 0.148 ms);
         // small P is launch-bound and prefers fewer passes.  Result must end in (key_a, val_a): A <- keys, then
@@ -704,12 +825,15 @@ hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* va
         const hipError_t rc = radix_pass<RADIX_BITS, SORT_ITEMS>(keys, nullptr, key_b, val_b, n, 0, hist, s, nullptr, tj);
         (void)radix_pass<RADIX_BITS, SORT_ITEMS>(key_b, val_b, key_a, val_a, n, 8, hist, s);
         (void)radix_pass<RADIX_BITS, SORT_ITEMS>(key_a, val_a, key_b, val_b, n, 16, hist, s);
-        (void)radix_pass<RADIX_BITS, SORT_ITEMS>(key_b, val_b, key_a, val_a, n, 24, hist, s);
+        (void)radix_pass<RADIX_BITS, SORT_ITEMS>(key_b, val_b, key_a, val_a, n, 24, hist, s, nullptr, nullptr, nullptr, payload);
+        if (payload) *counts_in_a = true;
         return rc;
     }
     const hipError_t rc = radix_pass<DEPTH_RADIX_BITS, SORT_ITEMS>(keys, nullptr, key_a, val_a, n, 0, hist, s, nullptr, tj);
     (void)radix_pass<DEPTH_RADIX_BITS, SORT_ITEMS>(key_a, val_a, key_b, val_b, n, DEPTH_RADIX_BITS, hist, s);
-    (void)radix_pass<DEPTH_RADIX_BITS, SORT_ITEMS>(key_b, val_b, key_a, val_a, n, 2 * DEPTH_RADIX_BITS, hist, s);
+    (void)radix_pass<DEPTH_RADIX_BITS, SORT_ITEMS>(key_b, val_b, key_a, val_a, n, 2 * DEPTH_RADIX_BITS, hist, s, nullptr, nullptr, nullptr,
+                                                   payload);
+    if (payload) *counts_in_a = true;
     return rc;
 }
 

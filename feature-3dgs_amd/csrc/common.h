@@ -56,6 +56,48 @@ constexpr int SMALL_SORT_MAX = 16384;                           // pairs the one
 constexpr int BIGQ_CAP = 1024;                                  // slots of the big-splat queue of the emit kernel (4 x 256: zeroed by four workgroups)
 constexpr int DEPTH_SORT_ITEMS = 8;                             // onesweep depth passes: 2048 keys per workgroup
 
+// Digits of the tile sort's multi-launch passes: as many passes as 8-bit digits would take (the A / B side arrangement of the
+// callers depends on that count), the key's bits spread evenly over them - 13 bits (1080p) are 7 + 6, not 8 + 8 with three
+// bits that are always zero: a ballot per bit and item less, half the histogram columns and row scans.
+struct DigitSplit {
+    int passes;
+    int width[4], shift[4];
+};
+constexpr DigitSplit tile_digit_split(int bits) {
+    DigitSplit s{};
+    s.passes = (bits + RADIX_BITS - 1) / RADIX_BITS;
+    const int w = s.passes ? (bits + s.passes - 1) / s.passes : 0;
+    int at = 0;
+    for (int p = 0; p < s.passes; p++) {
+        s.width[p] = p + 1 < s.passes ? w : bits - at;      // the last pass takes the rest
+        s.shift[p] = at;
+        at += s.width[p];
+    }
+    return s;
+}
+constexpr bool digit_split_ok(int bits) {
+    const DigitSplit s = tile_digit_split(bits);
+    if (s.passes != (bits + RADIX_BITS - 1) / RADIX_BITS) return false;        // the pass count of 8-bit digits
+    int at = 0;
+    for (int p = 0; p < s.passes; p++) {
+        if (s.shift[p] != at || s.width[p] < 1 || s.width[p] > RADIX_BITS) return false;      // contiguous, no wider than a digit
+        if (s.passes > 1 && s.width[p] < 4) return false;      // (4 ... 8 are instantiated; a single pass narrower than 4 ranks 4 bits)
+        at += s.width[p];
+    }
+    return at == bits;                                                          // every bit, once
+}
+constexpr bool digit_splits_ok() {
+    for (int bits = 1; bits <= 32; bits++)
+        if (!digit_split_ok(bits)) return false;
+    return true;
+}
+static_assert(digit_splits_ok(), "tile_digit_split: widths sum to the key's bits, each <= 8, contiguous shifts, ceil(bits / 8) passes");
+static_assert(tile_digit_split(13).width[0] == 7 && tile_digit_split(13).width[1] == 6 && tile_digit_split(13).shift[1] == 7, "13 = 7 + 6");
+static_assert(tile_digit_split(9).width[0] == 5 && tile_digit_split(9).width[1] == 4, "9 = 5 + 4");
+static_assert(tile_digit_split(15).width[0] == 8 && tile_digit_split(15).width[1] == 7, "15 = 8 + 7");
+static_assert(tile_digit_split(16).width[0] == 8 && tile_digit_split(16).width[1] == 8, "16 = 8 + 8");
+static_assert(tile_digit_split(8).passes == 1 && tile_digit_split(8).width[0] == 8 && tile_digit_split(5).width[0] == 5, "one pass: the bits themselves");
+
 inline size_t sort_blocks(size_t n) { return (n + SORT_CHUNK - 1) / SORT_CHUNK; }
 inline size_t scan_blocks(size_t n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK; }
 inline size_t depth_sort_blocks(size_t n) { return (n + SORT_THREADS * DEPTH_SORT_ITEMS - 1) / (SORT_THREADS * DEPTH_SORT_ITEMS); }
@@ -66,7 +108,10 @@ struct GeomState {
     uint8_t* clamped;         // P (bit0..2 = r,g,b clamped)
     uint32_t* tiles_touched;  // P
     uint32_t* depth_key;      // P   float bits of view-space depth, 0xFFFFFFFF when culled
-    uint32_t* key_a;          // P   ping-pong buffers of the depth sort
+    uint32_t* key_a;          // P   ping-pong buffers of the depth sort.  Behind the multi-launch depth sort key_a does NOT hold the sorted
+                              //     keys (nobody reads them) but tiles_touched in depth order - key_a[i] = tiles_touched[val_a[i]], stored by
+                              //     the sort's last scatter, which holds the id anyway - for the offset sums and the emit kernel to read in
+                              //     a row; the one-workgroup sort and the look-back flavour leave keys (or nothing) there
     uint32_t* key_b;
     uint32_t* val_a;
     uint32_t* val_b;
@@ -239,7 +284,9 @@ void launch_radix_sort_pairs(uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, 
 // `cap`: entries the instance arrays hold.  `n_dev` (null: cap IS the list length): the device's count - a frame whose count
 // exceeds cap stores nothing and raises `overflow` (device-visible host word, may be null).  The capacity is left in
 // GeomState::counters[3] for readers of the binning buffer.
-void launch_emit_instances(int P, const GeomState& g, const uint32_t* order, int gx, int gy, int2 band, int cull,
+// `counts_in_order` (optional): tiles_touched[order[i]] at i, where the depth sort left it (launch_depth_sort) - read beside
+// order[i] instead of behind it; null: gathered from g.tiles_touched.
+void launch_emit_instances(int P, const GeomState& g, const uint32_t* order, const uint32_t* counts_in_order, int gx, int gy, int2 band, int cull,
                            uint32_t* inst_tile, uint32_t* inst_id, uint2* ranges_enc, uint32_t* tile_len, uint32_t cap,
                            const uint32_t* n_dev, uint32_t* overflow, hipStream_t s);
 // single-pass flavour (option sort_onesweep): offsets by decoupled look-back inside the emit kernel, which also
@@ -266,9 +313,11 @@ struct TotalsJob {
     hipEvent_t ready;          // host side only
 };
 // `sums` (optional) / `sums_done`: see OffsetSumsJob - *sums_done says whether this call produced them
+// `counts_in_a` (optional, needs `sums`): the multi-launch sort's last pass stores sums->tiles_touched[id] at every id's place in
+// the order - into key_a, instead of the sorted keys - and sets *counts_in_a; the one-workgroup sort (sums_done) does not
 hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, uint32_t* val_b, size_t n,
                              uint32_t* hist, const TotalsJob* tj, hipStream_t s, const OffsetSumsJob* sums = nullptr,
-                             bool* sums_done = nullptr);
+                             bool* sums_done = nullptr, bool* counts_in_a = nullptr);
 void launch_iota(uint32_t* dst, size_t n, hipStream_t s);
 void launch_radix_sort_keys_to_order(const uint32_t* keys, uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, uint32_t* val_b,
                                      size_t n, int nbits, uint32_t* hist, hipStream_t s);

@@ -534,6 +534,7 @@ constexpr int EMIT_BIG = 512;       // tiles from which on a splat is emitted by
 __global__ void __launch_bounds__(256)
 emit_instances_kernel(int P, const uint32_t* __restrict__ order, const uint32_t* __restrict__ chunk_sums,
                       const uint32_t* __restrict__ sub, const uint32_t* __restrict__ tiles_touched,
+                      const uint32_t* __restrict__ counts_in_order,
                       const SplatRec* __restrict__ rec, int gx, int gy, int2 band, int cull, uint32_t* __restrict__ inst_tile,
                       uint32_t* __restrict__ inst_id, uint2* __restrict__ ranges_enc, uint32_t* __restrict__ tile_len,
                       uint32_t* __restrict__ big_ctl, uint2* __restrict__ big_items, uint32_t cap, uint32_t* __restrict__ cap_word,
@@ -558,7 +559,8 @@ emit_instances_kernel(int P, const uint32_t* __restrict__ order, const uint32_t*
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const bool valid = i < P;
     const uint32_t g = valid ? order[i] : 0u;
-    const uint32_t cnt = valid ? tiles_touched[g] : 0u;
+    // (counts_in_order: the depth sort left tiles_touched[order[i]] at i - one load beside order[i] instead of one behind it)
+    const uint32_t cnt = valid ? (counts_in_order ? counts_in_order[i] : tiles_touched[g]) : 0u;
     // the wave's range of the list starts behind the runs of 64 in front of its own inside its chunk of SCAN_CHUNK Gaussians
     // (binning.hip: scan_reduce_kernel); a lane's run starts behind the lanes in front of it
     const uint32_t first = (uint32_t)(blockIdx.x * 256 + 64 * w);              // the wave's first Gaussian (depth order)
@@ -1107,11 +1109,11 @@ void launch_preprocess(int P, int D, int M, const float* means3D, const float* s
                            g.depth_key, cull, g.ref_partial, g.depth_hist, g.big_ctl);
 }
 
-void launch_emit_instances(int P, const GeomState& g, const uint32_t* order, int gx, int gy, int2 band, int cull,
+void launch_emit_instances(int P, const GeomState& g, const uint32_t* order, const uint32_t* counts_in_order, int gx, int gy, int2 band, int cull,
                            uint32_t* inst_tile, uint32_t* inst_id, uint2* ranges_enc, uint32_t* tile_len, uint32_t cap,
                            const uint32_t* n_dev, uint32_t* overflow, hipStream_t s) {
     hipLaunchKernelGGL(emit_instances_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, order, g.scan_tmp, g.scan_sub,
-                       g.tiles_touched, g.rec, gx, gy, band, cull, inst_tile, inst_id, ranges_enc, tile_len, g.big_ctl, g.big_items,
+                       g.tiles_touched, counts_in_order, g.rec, gx, gy, band, cull, inst_tile, inst_id, ranges_enc, tile_len, g.big_ctl, g.big_items,
                        cap, g.counters + 3, n_dev, overflow);
 }
 
