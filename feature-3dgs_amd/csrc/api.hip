@@ -52,15 +52,17 @@ void note_frame(const void* geom, float axis_ratio, int band0, int band1) {
     if (g_frames.size() >= 256) g_frames.erase(g_frames.begin());
     g_frames.push_back({dev, geom, axis_ratio, band0, band1});
 }
-bool frame_axis_ratio(const void* geom, float* axis_ratio, int* band0 = nullptr, int* band1 = nullptr) {
+// The note of the forward call behind `geom`: its axis ratio, and the tile rows it listed, clamped to the grid of gy rows.  A
+// note that is gone (false): *axis_ratio untouched, the whole grid - right, only unbalanced.
+bool frame_note(const void* geom, int gy, float* axis_ratio, int* band0, int* band1) {
     int dev = 0;
     (void)hipGetDevice(&dev);
+    *band0 = 0; *band1 = gy;
     std::lock_guard<std::mutex> lk(g_frames_mu);
     for (const FrameNote& f : g_frames)
         if (f.device == dev && f.geom == geom) {
             *axis_ratio = f.axis_ratio;
-            if (band0) *band0 = f.band0;
-            if (band1) *band1 = f.band1;
+            clamp_band(f.band0, f.band1, gy, band0, band1);
             return true;
         }
     return false;
@@ -92,6 +94,36 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     g_err = buf;
     return code;
+}
+
+// The entry points that walk a finished forward call's lists (f3dgs_contributions, f3dgs_label_votes; `who` names one in the
+// messages): the checks they share of the call's sizes and of its state buffers ...
+int check_walk_call(const char* who, int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
+                    const char* image_buffer) {
+    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
+    if (R < 0 || width <= 0 || height <= 0)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: bad sizes (R = %d, image %d x %d)", who, R, width, height);
+    if (P > 0 && (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)))
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null state buffer", who);
+    return F3DGS_OK;
+}
+// ... and what the launchers read of that state.  P == 0: no forward state, every tile is empty.  The sorted list sits at
+// offset 0 of the binning buffer whatever length it was carved for (BinState::list_of); where nothing was rendered the buffer
+// may be null: every range is empty and the list is never read.
+WalkArgs walk_args(int P, int width, int height, const char* geom_buffer, const char* binning_buffer, const char* image_buffer) {
+    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
+    WalkArgs a = {nullptr, nullptr, nullptr, nullptr, width, height, gx, gy, 0u, 0u};
+    if (P == 0) return a;
+    const ImageState img = ImageState::carve(const_cast<char*>(image_buffer), (size_t)width * height, (size_t)gx * gy, nullptr);
+    a.ranges = img.ranges;
+    a.n_contrib = img.n_contrib;
+    a.rec = GeomState::carve(const_cast<char*>(geom_buffer), P, nullptr).rec;
+    a.point_list = binning_buffer ? BinState::list_of(binning_buffer) : nullptr;
+    float long_axis = 0.f;
+    int b0, b1;
+    frame_note(geom_buffer, gy, &long_axis, &b0, &b1);
+    band_perm_params(gx, gy, b0, b1, &a.band_b0, &a.band_tb);
+    return a;
 }
 
 }  // namespace
@@ -434,7 +466,8 @@ int f3dgs_set_feature_grad_lowres(const float* gx, int Hg, int Wg, const float* 
 
 int f3dgs_debug_band_order(int gx, int gy, int tile_row_begin, int tile_row_end, uint32_t* tiles_out) {
     if (gx <= 0 || gy <= 0 || !tiles_out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "bad grid");
-    const int b0r = std::min(std::max(tile_row_begin, 0), gy), b1r = std::min(std::max(tile_row_end, b0r), gy);
+    int b0r, b1r;
+    clamp_band(tile_row_begin, tile_row_end, gy, &b0r, &b1r);
     uint32_t b0 = 0, tb = 0;
     band_perm_params(gx, gy, b0r, b1r, &b0, &tb);
     const uint32_t T = (uint32_t)gx * (uint32_t)gy;
@@ -504,10 +537,8 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
     fill_view(vp, viewmatrix, projmatrix, cam_pos, background, tan_fovx, tan_fovy, width, height, scale_modifier);
     // (one part in a thousand of slack on the ratio: a scene built with scales of exactly 16 : 1 stays on the bf16 side)
     vp.max_axis_ratio = 1.001f * (float)options().bwd_bf16_max_ratio;
-    if (g_band_begin != 0 || g_band_end != 0) {      // a tile band of the view (f3dgs.h: f3dgs_set_tile_band); begin >= end: an empty one
-        vp.band0 = std::min(std::max(g_band_begin, 0), vp.gy);
-        vp.band1 = std::min(std::max(g_band_end, vp.band0), vp.gy);
-    }
+    // a tile band of the view (f3dgs.h: f3dgs_set_tile_band); begin >= end: an empty one
+    if (g_band_begin != 0 || g_band_end != 0) clamp_band(g_band_begin, g_band_end, vp.gy, &vp.band0, &vp.band1);
     const int2 band = make_int2(vp.band0, vp.band1);
     const size_t tiles = (size_t)vp.gx * vp.gy;
 
@@ -760,9 +791,7 @@ int f3dgs_backward(int P, int D, int M, int C, int R, const float* background, i
     int contraction = options().bwd_bf16 > 0 ? 1 : 0;
     {
         float long_axis = 1.f;       // what the forward call of this frame noted (against bwd_bf16_max_ratio as it was THEN)
-        int b0 = 0, b1 = vp.gy;      // ... and the tile rows it listed (a note that is gone: the whole grid - right, only unbalanced)
-        const bool noted = frame_axis_ratio(geom_buffer, &long_axis, &b0, &b1);
-        if (noted) { vp.band0 = std::min(std::max(b0, 0), vp.gy); vp.band1 = std::min(std::max(b1, vp.band0), vp.gy); }
+        const bool noted = frame_note(geom_buffer, vp.gy, &long_axis, &vp.band0, &vp.band1);      // ... and the tile rows it listed
         if (options().bwd_bf16 < 0) {
             contraction = (noted && long_axis == 0.f) ? 1 : 2;
             if (noted && long_axis == 2.f) contraction = 3;     // a captured frame: decided on the device (GeomState::counters[2])
@@ -805,34 +834,18 @@ int f3dgs_contributions(int P, int R, int width, int height, const char* geom_bu
                         const char* image_buffer, int K, const float* masks, float* acc, float* wmax, float* alpha,
                         float* median_depth, int* ids, float* id_weight, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: P < 0");
-    if (R < 0 || width <= 0 || height <= 0)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: bad sizes (R = %d, image %d x %d)", R, width, height);
+    if (int rc = check_walk_call("f3dgs_contributions", P, R, width, height, geom_buffer, binning_buffer, image_buffer)) return rc;
     if (K < 0 || K > F3DGS_CONTRIB_MAX_MASKS)
         return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d masks, 0 .. %d are taken per call", K, F3DGS_CONTRIB_MAX_MASKS);
     if (K > 0 && !masks) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d but masks is null", K);
     if (K > 0 && !acc) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d masks but acc is null", K);
-    if (P > 0 && (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: null state buffer");
     if (!acc && !wmax && !alpha && !median_depth && !ids && !id_weight)
         return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: every output is null");
     if (P == 0) {      // no forward state: nothing blended anywhere; the per-Gaussian outputs have no rows
         if (!alpha && !median_depth && !ids && !id_weight) return F3DGS_OK;
-        HIP_TRY(launch_contributions(width, height, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, alpha,
-                                     median_depth, ids, id_weight, s));
-        return F3DGS_OK;
+        K = 0; masks = nullptr; acc = wmax = nullptr;
     }
-    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
-    const size_t HW = (size_t)width * height, tiles = (size_t)gx * gy;
-    const GeomState geom = GeomState::carve(const_cast<char*>(geom_buffer), P, nullptr);
-    const ImageState img = ImageState::carve(const_cast<char*>(image_buffer), HW, tiles, nullptr);
-    // the sorted list sits at offset 0 of the binning buffer whatever length it was carved for (BinState::list_of); with R = 0
-    // every range is empty and it is never read
-    const uint32_t* point_list = binning_buffer ? BinState::list_of(binning_buffer) : nullptr;
-    float long_axis = 0.f;
-    int b0 = 0, b1 = gy;      // the tile rows the forward call listed (a note that is gone: the whole grid - right, only unbalanced)
-    if (frame_axis_ratio(geom_buffer, &long_axis, &b0, &b1)) { b0 = std::min(std::max(b0, 0), gy); b1 = std::min(std::max(b1, b0), gy); }
-    HIP_TRY(launch_contributions(width, height, b0, b1, img.ranges, point_list, geom.rec, img.n_contrib, K, masks, acc, wmax, alpha,
+    HIP_TRY(launch_contributions(walk_args(P, width, height, geom_buffer, binning_buffer, image_buffer), K, masks, acc, wmax, alpha,
                                  median_depth, ids, id_weight, s));
     return F3DGS_OK;
 }
@@ -840,9 +853,7 @@ int f3dgs_contributions(int P, int R, int width, int height, const char* geom_bu
 int f3dgs_label_votes(int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
                       const char* image_buffer, const void* labels, int labels_format, int L, float* acc, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: P < 0");
-    if (R < 0 || width <= 0 || height <= 0)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: bad sizes (R = %d, image %d x %d)", R, width, height);
+    if (int rc = check_walk_call("f3dgs_label_votes", P, R, width, height, geom_buffer, binning_buffer, image_buffer)) return rc;
     if (L < 1 || L > F3DGS_LABEL_VOTES_MAX_LABELS)
         return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: L = %d labels, 1 .. %d are taken", L, F3DGS_LABEL_VOTES_MAX_LABELS);
     if (labels_format != F3DGS_LABELS_U8 && labels_format != F3DGS_LABELS_I32 && labels_format != F3DGS_LABELS_I64)
@@ -852,18 +863,8 @@ int f3dgs_label_votes(int P, int R, int width, int height, const char* geom_buff
     const uintptr_t elem = labels_format == F3DGS_LABELS_U8 ? 1 : labels_format == F3DGS_LABELS_I32 ? 4 : 8;
     if (reinterpret_cast<uintptr_t>(labels) % elem)
         return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: labels is off the alignment of its %d-byte element", (int)elem);
-    if (P > 0 && (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: null state buffer");
     if (P == 0 || R == 0) return F3DGS_OK;      // nothing blended anywhere: nothing to add
-    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
-    const size_t HW = (size_t)width * height, tiles = (size_t)gx * gy;
-    const GeomState geom = GeomState::carve(const_cast<char*>(geom_buffer), P, nullptr);
-    const ImageState img = ImageState::carve(const_cast<char*>(image_buffer), HW, tiles, nullptr);
-    float long_axis = 0.f;
-    int b0 = 0, b1 = gy;      // the tile rows the forward call listed, as f3dgs_contributions finds them
-    if (frame_axis_ratio(geom_buffer, &long_axis, &b0, &b1)) { b0 = std::min(std::max(b0, 0), gy); b1 = std::min(std::max(b1, b0), gy); }
-    HIP_TRY(launch_label_votes(width, height, b0, b1, img.ranges, BinState::list_of(binning_buffer), geom.rec, img.n_contrib, labels,
-                               labels_format, L, acc, s));
+    HIP_TRY(launch_label_votes(walk_args(P, width, height, geom_buffer, binning_buffer, image_buffer), labels, labels_format, L, acc, s));
     return F3DGS_OK;
 }
 

@@ -774,6 +774,21 @@ EditSelect(torch::Tensor& features, const torch::Tensor& text, uint64_t positive
     return std::make_tuple(mask, score, op_out);
 }
 
+// What the operators over the state buffers of a rasterize_gaussians call (contributions, label_votes; `op` names one in the
+// messages) check alike: the buffers and the sizes ...
+void check_walk_state(const char* op, const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imgBuffer,
+                      int64_t P, int64_t H, int64_t W) {
+    TORCH_CHECK(imgBuffer.is_cuda() && geomBuffer.is_cuda() && binningBuffer.is_cuda(), op,
+                ": the state buffers must live on a HIP device (no CPU path)");
+    TORCH_CHECK(P >= 0 && H > 0 && W > 0 && H * W < (1ll << 31), op, ": bad sizes P = ", P, ", image ", H, " x ", W);
+}
+// ... and that an operand lives where they do
+void check_on_state_device(const char* op, const torch::Tensor& t, const char* name, const torch::Device& dev) {
+    TORCH_CHECK(t.is_cuda() && t.device() == dev, op, ": ", name, " must live on the HIP device of the state buffers (got ", t.device(), ")");
+}
+// a state buffer as the library takes it (an empty one: null)
+const char* state_ptr(const torch::Tensor& t) { return t.numel() ? reinterpret_cast<const char*>(t.data_ptr()) : nullptr; }
+
 // the contribution pass (include/f3dgs.h: f3dgs_contributions) over the state buffers of a rasterize_gaussians call: masks
 // (K, H, W) float32 or None; acc (P, K + 1) float32, added to, or None; wmax (P) float32, max-ed into, or None; want_pixel: the
 // four per-pixel outputs.  Returns (alpha, median_depth, ids, id_weight), each (H, W), or four None.
@@ -781,13 +796,10 @@ std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::opti
 Contributions(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imgBuffer, int64_t P,
               int64_t num_rendered, int64_t H, int64_t W, const c10::optional<torch::Tensor>& masks, c10::optional<torch::Tensor> acc,
               c10::optional<torch::Tensor> wmax, bool want_pixel) {
-    TORCH_CHECK(imgBuffer.is_cuda() && geomBuffer.is_cuda() && binningBuffer.is_cuda(),
-                "contributions: the state buffers must live on a HIP device (no CPU path)");
-    TORCH_CHECK(P >= 0 && H > 0 && W > 0 && H * W < (1ll << 31), "contributions: bad sizes P = ", P, ", image ", H, " x ", W);
+    check_walk_state("contributions", geomBuffer, binningBuffer, imgBuffer, P, H, W);
     const auto dev = imgBuffer.device();
     auto on_dev_f32 = [&](const torch::Tensor& t, const char* name) {
-        TORCH_CHECK(t.is_cuda() && t.device() == dev, "contributions: ", name, " must live on the HIP device of the state buffers (got ",
-                    t.device(), ")");
+        check_on_state_device("contributions", t, name, dev);
         TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous(), "contributions: ", name, " must be contiguous float32");
     };
     int64_t K = 0;
@@ -818,12 +830,11 @@ Contributions(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffe
         ids = torch::empty({H, W}, imgBuffer.options().dtype(torch::kInt32));
         id_weight = torch::empty({H, W}, f32);
     }
-    auto state = [](const torch::Tensor& t) { return t.numel() ? reinterpret_cast<const char*>(t.data_ptr()) : nullptr; };
     const bool per_gaussian = P > 0;      // (P, .) tensors of no rows have no storage: nothing to add to
     if (!per_gaussian) K = 0;
     if (!per_gaussian && !want_pixel) return std::make_tuple(alpha, median, ids, id_weight);
     const int rc = f3dgs_contributions(
-        (int)P, (int)num_rendered, (int)W, (int)H, state(geomBuffer), state(binningBuffer), state(imgBuffer), (int)K,
+        (int)P, (int)num_rendered, (int)W, (int)H, state_ptr(geomBuffer), state_ptr(binningBuffer), state_ptr(imgBuffer), (int)K,
         K ? masks->data_ptr<float>() : nullptr, (acc.has_value() && per_gaussian) ? acc->data_ptr<float>() : nullptr,
         (wmax.has_value() && per_gaussian) ? wmax->data_ptr<float>() : nullptr, want_pixel ? alpha->data_ptr<float>() : nullptr,
         want_pixel ? median->data_ptr<float>() : nullptr, want_pixel ? ids->data_ptr<int>() : nullptr,
@@ -836,14 +847,11 @@ Contributions(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffe
 // int32 / int64; acc (P, L + 1) float32, added to
 void LabelVotes(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imgBuffer, int64_t P,
                 int64_t num_rendered, int64_t H, int64_t W, const torch::Tensor& labels, int64_t L, torch::Tensor& acc) {
-    TORCH_CHECK(imgBuffer.is_cuda() && geomBuffer.is_cuda() && binningBuffer.is_cuda(),
-                "label_votes: the state buffers must live on a HIP device (no CPU path)");
-    TORCH_CHECK(P >= 0 && H > 0 && W > 0 && H * W < (1ll << 31), "label_votes: bad sizes P = ", P, ", image ", H, " x ", W);
+    check_walk_state("label_votes", geomBuffer, binningBuffer, imgBuffer, P, H, W);
     TORCH_CHECK(L >= 1 && L <= F3DGS_LABEL_VOTES_MAX_LABELS, "label_votes: L = ", L, " labels, 1 .. ", F3DGS_LABEL_VOTES_MAX_LABELS, " are taken");
     const auto dev = imgBuffer.device();
     const auto st = labels.scalar_type();
-    TORCH_CHECK(labels.is_cuda() && labels.device() == dev, "label_votes: labels must live on the HIP device of the state buffers (got ",
-                labels.device(), ")");
+    check_on_state_device("label_votes", labels, "labels", dev);
     TORCH_CHECK((st == torch::kUInt8 || st == torch::kInt32 || st == torch::kInt64) && labels.is_contiguous() && labels.dim() == 2 &&
                     labels.size(0) == H && labels.size(1) == W,
                 "label_votes: labels must be contiguous uint8, int32 or int64 (", H, ", ", W, "), got ", st, " ", labels.sizes());
@@ -852,10 +860,9 @@ void LabelVotes(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuf
                 "label_votes: acc must be contiguous float32 (", P, ", ", L + 1, ") on the device of the state buffers, got ", acc.sizes());
     if (P == 0) return;      // a (0, .) tensor has no storage: nothing to add to
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    auto state = [](const torch::Tensor& t) { return t.numel() ? reinterpret_cast<const char*>(t.data_ptr()) : nullptr; };
     const int format = st == torch::kUInt8 ? F3DGS_LABELS_U8 : st == torch::kInt32 ? F3DGS_LABELS_I32 : F3DGS_LABELS_I64;
-    const int rc = f3dgs_label_votes((int)P, (int)num_rendered, (int)W, (int)H, state(geomBuffer), state(binningBuffer), state(imgBuffer),
-                                     labels.data_ptr(), format, (int)L, acc.data_ptr<float>(), current_stream(imgBuffer));
+    const int rc = f3dgs_label_votes((int)P, (int)num_rendered, (int)W, (int)H, state_ptr(geomBuffer), state_ptr(binningBuffer),
+                                     state_ptr(imgBuffer), labels.data_ptr(), format, (int)L, acc.data_ptr<float>(), current_stream(imgBuffer));
     check_status(rc, "label_votes");
 }
 

@@ -409,14 +409,20 @@ int launch_render_backward(const ViewParams& vp, int C, const uint2* ranges, con
                            const float* dL_dpix, const float* dL_dfeat, const float* dL_ddepth, float* grec,
                            float* dL_dfeature, const uint32_t* tile_len, uint32_t* tile_order, const LowresGrad* lowres,
                            int contraction, const uint32_t* gate, hipStream_t s);      // (vp.band0 / band1: the forward call's band, see band_perm)
-// contrib.hip: the contribution pass over a finished forward call's lists (f3dgs_contributions).  `ranges` null: no forward
-// state (P == 0), every tile empty.  band0 / band1: the forward call's band (workgroup order only, see band_perm).
-hipError_t launch_contributions(int W, int H, int band0, int band1, const uint2* ranges, const uint32_t* point_list, const SplatRec* rec,
-                                const uint32_t* n_contrib, int K, const float* masks, float* acc, float* wmax, float* alpha,
+// What a walk over a finished forward call's lists needs of the call (api.hip fills it from the state buffers)
+struct WalkArgs {
+    const uint2* ranges;          // null: no forward state (P == 0) - every tile is empty
+    const uint32_t* point_list;
+    const SplatRec* rec;
+    const uint32_t* n_contrib;
+    int W, H, gx, gy;
+    uint32_t band_b0, band_tb;    // band_perm: the forward call's band (workgroup order only), (0, 0) = whole view
+};
+// contrib.hip: the contribution pass over those lists (f3dgs_contributions)
+hipError_t launch_contributions(const WalkArgs& walk, int K, const float* masks, float* acc, float* wmax, float* alpha,
                                 float* median_depth, int* ids, float* id_weight, hipStream_t s);
 // contrib.hip: the label vote over the same lists (f3dgs_label_votes): acc (P x (L + 1)) over the one-hot masks of `labels`
-hipError_t launch_label_votes(int W, int H, int band0, int band1, const uint2* ranges, const uint32_t* point_list, const SplatRec* rec,
-                              const uint32_t* n_contrib, const void* labels, int format, int L, float* acc, hipStream_t s);
+hipError_t launch_label_votes(const WalkArgs& walk, const void* labels, int format, int L, float* acc, hipStream_t s);
 struct BwdArgs;
 void launch_render_backward_pl(BwdArgs a, int C, hipStream_t s);     // render_bwd_pl.hip
 void launch_tile_order(const uint32_t* tile_len, size_t tiles, uint32_t* order, uint32_t band_b0, uint32_t band_tb, hipStream_t s);
@@ -458,6 +464,11 @@ __host__ __device__ __forceinline__ uint32_t band_perm(uint32_t v, uint32_t T, u
     return j < b0 ? j : j + tb;
 }
 #endif
+// tile rows [begin, end) as asked for, clamped to a grid of gy rows: begin in [0, gy], end in [begin, gy]
+inline void clamp_band(int begin, int end, int gy, int* band0, int* band1) {
+    *band0 = std::min(std::max(begin, 0), gy);
+    *band1 = std::min(std::max(end, *band0), gy);
+}
 // host side: (first tile, tiles) of the band for band_perm, or (0, 0) where the relabelling is off (whole view, a band of
 // more than half the grid, a grid too small to matter)
 inline void band_perm_params(int gx, int gy, int band0, int band1, uint32_t* b0, uint32_t* tb) {

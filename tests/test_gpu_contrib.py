@@ -186,6 +186,28 @@ def test_case_against_the_forward_and_both_judges(name, option, oracle_lib):
         assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("name", ["ragged", "chunks"])
+def test_every_column_count_walks_the_same_list(name):
+    """One walk feeds every contrib_kernel<NC, PIX>, with the entry's depth (PIX) and without: the reproducible outputs - the
+    four per-pixel ones, and wmax, a max of non-negative floats - must not depend on which instantiation formed them."""
+    sc = CASES[name]()
+    W, H, P = sc["image_width"], sc["image_height"], sc["P"]
+    masks = _masks(W, H)
+    fwd = _forward(sc)
+    pix_only = [_np(t) for t in _pass(sc, fwd)]                                   # <0, true>
+    wmax_only = _zeros(P)
+    assert _pass(sc, fwd, None, None, wmax_only, pixel=False) == (None, None, None, None)      # <0, false>
+    assert pix_only[0].any() and wmax_only.any()
+    for k in (0, 1, 3, 7):                                                        # NC = 1, 2, 4, 8
+        m = masks[:k] if k else None
+        pix = _pass(sc, fwd, m, _zeros(P, k + 1), None)                           # <NC, true>
+        for what, a, b in zip(("alpha", "median_depth", "ids", "id_weight"), pix, pix_only):
+            assert np.array_equal(_np(a).view(np.uint32), b.view(np.uint32)), f"{name}: {what} with K = {k} differs from the per-pixel-only call"
+        wmax = _zeros(P)
+        _pass(sc, fwd, m, _zeros(P, k + 1), wmax, pixel=False)                    # <NC, false>
+        assert torch.equal(wmax.view(torch.int32), wmax_only.view(torch.int32)), f"{name}: wmax beside K = {k} differs from the wmax-only call"
+
+
 def test_no_gaussians_and_nothing_in_front_of_the_camera():
     import contrib
     import diff_gaussian_rasterization as dgr
