@@ -23,6 +23,9 @@ classes it has (f3dgs_label_votes), without the (L, H, W) one-hot stack:
         lifter.add_view(cam, gaussians, pipe, bg, label_map_of(cam))    # (H, W) uint8 / int32 / int64
     edit.apply_edit(opacity, shs, lifter.select(cls), {"deletion": True});  picture = lifter.label_image(ids)
 
+Instance maps whose ids are NOT consistent between views (SAM's) go through instances.InstanceLifter, a LabelLifter that
+associates every view's masks with the 3D instances built so far before it adds them.
+
 HIP only; no CPU fallback.  Nothing is read back to the host.
 """
 from __future__ import annotations

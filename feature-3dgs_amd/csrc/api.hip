@@ -417,7 +417,7 @@ CountReadback* count_readback(hipStream_t s, bool may_create) {
 
 extern "C" {
 
-int f3dgs_version(void) { return 31600; }   // 3.16.0 (major * 10000 + minor * 100 + patch): 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
+int f3dgs_version(void) { return 31700; }   // 3.17.0 (major * 10000 + minor * 100 + patch): 3.17 f3dgs_instance_associate, f3dgs_instance_merge; 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
 
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 
@@ -865,6 +865,43 @@ int f3dgs_label_votes(int P, int R, int width, int height, const char* geom_buff
         return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: labels is off the alignment of its %d-byte element", (int)elem);
     if (P == 0 || R == 0) return F3DGS_OK;      // nothing blended anywhere: nothing to add
     HIP_TRY(launch_label_votes(walk_args(P, width, height, geom_buffer, binning_buffer, image_buffer), labels, labels_format, L, acc, s));
+    return F3DGS_OK;
+}
+
+// nullptr if the sizes are taken, else the reason
+static const char* instance_bad_sizes(int P, int M, int L) {
+    if (P < 0) return "%s: P < 0 (P = %d, M = %d, L = %d)";
+    if (M < 1 || M > F3DGS_INSTANCE_MAX_MASKS) return "%s: bad sizes: M outside 1 .. 1024 (P = %d, M = %d, L = %d)";
+    if (L < 1 || L > F3DGS_INSTANCE_MAX_INSTANCES) return "%s: bad sizes: L outside 1 .. 4096 (P = %d, M = %d, L = %d)";
+    return nullptr;
+}
+
+size_t f3dgs_instance_scratch_bytes(int M, int L) {
+    if (instance_bad_sizes(0, M, L)) return 0;
+    return instance_scratch_bytes(M, L);
+}
+
+int f3dgs_instance_associate(int P, int M, int L, const float* acc_view, const float* acc, double iou_thresh, double min_weight,
+                             int32_t* count, int32_t* dropped, int32_t* mapping, int32_t* best_label, double* best_iou, float* table,
+                             void* scratch, void* stream) {
+    const char* who = "f3dgs_instance_associate";
+    if (const char* why = instance_bad_sizes(P, M, L)) return fail(F3DGS_ERR_INVALID_ARGUMENT, why, who, P, M, L);
+    if (!(iou_thresh >= 0.0)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: iou_thresh is negative or NaN", who);
+    if (!(min_weight >= 0.0)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: min_weight is negative or NaN", who);
+    if (!count || !dropped || !mapping || !best_label || !best_iou || !table || !scratch || (P > 0 && (!acc_view || !acc)))
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (!aligned16(scratch)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+    HIP_TRY(launch_instance_associate(P, M, L, acc_view, acc, iou_thresh, min_weight, count, dropped, mapping, best_label, best_iou, table,
+                                      static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_instance_merge(int P, int M, int L, float* acc_view, int clear_view, const int32_t* mapping, float* acc, void* stream) {
+    const char* who = "f3dgs_instance_merge";
+    if (const char* why = instance_bad_sizes(P, M, L)) return fail(F3DGS_ERR_INVALID_ARGUMENT, why, who, P, M, L);
+    if (!mapping || (P > 0 && (!acc_view || !acc))) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (P == 0) return F3DGS_OK;      // no rows: nothing to add
+    HIP_TRY(launch_instance_merge(P, M, L, acc_view, clear_view != 0, mapping, acc, static_cast<hipStream_t>(stream)));
     return F3DGS_OK;
 }
 

@@ -866,6 +866,70 @@ void LabelVotes(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuf
     check_status(rc, "label_votes");
 }
 
+// What instance_associate and instance_merge (`op` names one in the messages) check alike: acc_view (P, M + 1) and acc (P, L + 1),
+// contiguous float32 on one HIP device.  Returns (P, M, L).
+std::tuple<int64_t, int64_t, int64_t> check_instance_votes(const char* op, const torch::Tensor& acc_view, const torch::Tensor& acc) {
+    TORCH_CHECK(acc_view.is_cuda() && acc.is_cuda(), op, ": acc_view and acc must live on a HIP device (no CPU path)");
+    TORCH_CHECK(acc.device() == acc_view.device(), op, ": acc on ", acc.device(), ", acc_view on ", acc_view.device());
+    TORCH_CHECK(acc_view.scalar_type() == torch::kFloat32 && acc_view.is_contiguous() && acc_view.dim() == 2 && acc_view.size(1) >= 2, op,
+                ": acc_view must be contiguous float32 (P, M + 1), got ", acc_view.scalar_type(), " ", acc_view.sizes());
+    TORCH_CHECK(acc.scalar_type() == torch::kFloat32 && acc.is_contiguous() && acc.dim() == 2 && acc.size(1) >= 2 && acc.size(0) == acc_view.size(0),
+                op, ": acc must be contiguous float32 (", acc_view.size(0), ", L + 1), got ", acc.scalar_type(), " ", acc.sizes());
+    const int64_t P = acc_view.size(0), M = acc_view.size(1) - 1, L = acc.size(1) - 1;
+    TORCH_CHECK(P < (1ll << 31), op, ": P = ", P, " rows");
+    TORCH_CHECK(M <= F3DGS_INSTANCE_MAX_MASKS, op, ": M = ", M, " masks, 1 .. ", F3DGS_INSTANCE_MAX_MASKS, " are taken");
+    TORCH_CHECK(L <= F3DGS_INSTANCE_MAX_INSTANCES, op, ": L = ", L, " instances, 1 .. ", F3DGS_INSTANCE_MAX_INSTANCES, " are taken");
+    return std::make_tuple(P, M, L);
+}
+
+// association of a view's masks with the 3D instances (include/f3dgs.h: f3dgs_instance_associate).  count, dropped: int32 tensors
+// of one element on the device, updated in place.  Returns (mapping (M) int32, best_label (M) int32, best_iou (M) float64,
+// table (M + 1, L + 1) float32).
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+InstanceAssociate(const torch::Tensor& acc_view, const torch::Tensor& acc, torch::Tensor& count, torch::Tensor& dropped, double iou_thresh,
+                  double min_weight) {
+    int64_t P, M, L;
+    std::tie(P, M, L) = check_instance_votes("instance_associate", acc_view, acc);
+    const auto dev = acc_view.device();
+    auto counter = [&](const torch::Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == torch::kInt32 && t.numel() == 1 && t.is_contiguous(),
+                    "instance_associate: ", name, " must be one int32 on the device of acc_view, got ", t.scalar_type(), " ", t.sizes(), " on ",
+                    t.device());
+    };
+    counter(count, "count");
+    counter(dropped, "dropped");
+    TORCH_CHECK(iou_thresh >= 0.0 && min_weight >= 0.0, "instance_associate: iou_thresh and min_weight must be >= 0 (got ", iou_thresh, ", ",
+                min_weight, ")");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    auto i32 = acc_view.options().dtype(torch::kInt32);
+    torch::Tensor mapping = torch::empty({M}, i32), best_label = torch::empty({M}, i32);
+    torch::Tensor best_iou = torch::empty({M}, acc_view.options().dtype(torch::kFloat64));
+    torch::Tensor table = torch::empty({M + 1, L + 1}, acc_view.options());
+    torch::Tensor scratch = torch::empty({(long long)f3dgs_instance_scratch_bytes((int)M, (int)L)}, acc_view.options().dtype(torch::kByte));
+    const int rc = f3dgs_instance_associate((int)P, (int)M, (int)L, P ? acc_view.data_ptr<float>() : nullptr, P ? acc.data_ptr<float>() : nullptr,
+                                            iou_thresh, min_weight, count.data_ptr<int>(), dropped.data_ptr<int>(), mapping.data_ptr<int>(),
+                                            best_label.data_ptr<int>(), best_iou.data_ptr<double>(), table.data_ptr<float>(),
+                                            scratch.data_ptr(), current_stream(acc_view));
+    check_status(rc, "instance_associate");
+    return std::make_tuple(mapping, best_label, best_iou, table);
+}
+
+// the merge under a mapping (include/f3dgs.h: f3dgs_instance_merge): acc is added to; acc_view is cleared where it was read as
+// non-zero with clear_view
+void InstanceMerge(torch::Tensor& acc_view, const torch::Tensor& mapping, torch::Tensor& acc, bool clear_view) {
+    int64_t P, M, L;
+    std::tie(P, M, L) = check_instance_votes("instance_merge", acc_view, acc);
+    TORCH_CHECK(mapping.is_cuda() && mapping.device() == acc_view.device() && mapping.scalar_type() == torch::kInt32 && mapping.is_contiguous() &&
+                    mapping.dim() == 1 && mapping.size(0) == M,
+                "instance_merge: mapping must be contiguous int32 (", M, ") on the device of acc_view, got ", mapping.scalar_type(), " ",
+                mapping.sizes(), " on ", mapping.device());
+    if (P == 0) return;      // a (0, .) tensor has no storage: nothing to add to
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(acc_view.device());
+    const int rc = f3dgs_instance_merge((int)P, (int)M, (int)L, acc_view.data_ptr<float>(), clear_view ? 1 : 0, mapping.data_ptr<int>(),
+                                        acc.data_ptr<float>(), current_stream(acc_view));
+    check_status(rc, "instance_merge");
+}
+
 // open-vocabulary segmentation (include/f3dgs.h: f3dgs_segment).  feature_map (C,H,W), text (K,Cout) float32; weight (Cout,C) /
 // bias (Cout) or empty tensors.  Returns (labels (Hs,Ws) int64, score (Hs,Ws) float32 or None).
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>>
@@ -1203,6 +1267,11 @@ PYBIND11_MODULE(_C, m) {
     m.def("label_votes", &LabelVotes, py::arg("geomBuffer"), py::arg("binningBuffer"), py::arg("imgBuffer"), py::arg("P"),
           py::arg("num_rendered"), py::arg("H"), py::arg("W"), py::arg("labels"), py::arg("L"), py::arg("acc"));
     m.attr("LABEL_VOTES_MAX_LABELS") = (int)F3DGS_LABEL_VOTES_MAX_LABELS;
+    m.def("instance_associate", &InstanceAssociate, py::arg("acc_view"), py::arg("acc"), py::arg("count"), py::arg("dropped"),
+          py::arg("iou_thresh"), py::arg("min_weight"));
+    m.def("instance_merge", &InstanceMerge, py::arg("acc_view"), py::arg("mapping"), py::arg("acc"), py::arg("clear_view"));
+    m.attr("INSTANCE_MAX_MASKS") = (int)F3DGS_INSTANCE_MAX_MASKS;
+    m.attr("INSTANCE_MAX_INSTANCES") = (int)F3DGS_INSTANCE_MAX_INSTANCES;
     m.def("feature_pca_moments", &FeaturePcaMoments, py::arg("feature_map"), py::arg("stride"));
     m.def("feature_pca_project", &FeaturePcaProject, py::arg("feature_map"), py::arg("mean"), py::arg("components"),
           py::arg("lo") = py::none(), py::arg("hi") = py::none());

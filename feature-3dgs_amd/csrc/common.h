@@ -423,6 +423,12 @@ hipError_t launch_contributions(const WalkArgs& walk, int K, const float* masks,
                                 float* median_depth, int* ids, float* id_weight, hipStream_t s);
 // contrib.hip: the label vote over the same lists (f3dgs_label_votes): acc (P x (L + 1)) over the one-hot masks of `labels`
 hipError_t launch_label_votes(const WalkArgs& walk, const void* labels, int format, int L, float* acc, hipStream_t s);
+// instances.hip: one view's masks against the 3D instances built so far (f3dgs_instance_associate, f3dgs_instance_merge)
+size_t instance_scratch_bytes(int M, int L);
+hipError_t launch_instance_associate(int P, int M, int L, const float* acc_view, const float* acc, double iou_thresh, double min_weight,
+                                     int* count, int* dropped, int* mapping, int* best_label, double* best_iou, float* table,
+                                     char* scratch, hipStream_t s);
+hipError_t launch_instance_merge(int P, int M, int L, float* acc_view, bool clear_view, const int* mapping, float* acc, hipStream_t s);
 struct BwdArgs;
 void launch_render_backward_pl(BwdArgs a, int C, hipStream_t s);     // render_bwd_pl.hip
 void launch_tile_order(const uint32_t* tile_len, size_t tiles, uint32_t* order, uint32_t band_b0, uint32_t band_tb, hipStream_t s);

@@ -491,6 +491,52 @@ int f3dgs_label_votes(int P, int R, int width, int height,
                       float* acc /* P x (L + 1), ADDED TO */, void* stream /* hipStream_t */);
 
 /*
+ * Association of one view's instances with the 3D instances built so far (no counterpart in the reference).  A segmenter such
+ * as SAM numbers its masks afresh in every view; these two calls carry the ids of M view masks over to L global instance slots,
+ * on dense matrices alone (no tile list is touched).
+ *   acc_view  (P, M + 1) floats: what f3dgs_label_votes wrote for this view with L = M (column M: the weight total)
+ *   acc       (P, L + 1) floats: the global accumulator, laid out alike (column L: the weight total)
+ *   count     a DEVICE int32: the instance slots in use, 0 <= count <= L; updated by the call
+ *   dropped   a DEVICE int32, INCREASED by the number of masks that found no free slot
+ * f3dgs_instance_associate.  Only Gaussians with acc_view[g][M] > 0 (seen in this view) take part.
+ *   3D label  gl[g] = the lowest index of the largest of acc[g][0..L), or -1 when that maximum is <= 0
+ *   table     T, (M + 1) x (L + 1) floats, an OUTPUT, fully written: T[m][c] += acc_view[g][m] for m < M with c = gl[g], or c = L
+ *             when gl[g] == -1; row M receives max(0, acc_view[g][M] - sum_m acc_view[g][m]), the weight under no mask, formed
+ *             per Gaussian in fp32 in ascending m.  Float atomics in a varying order: not bit-reproducible between runs
+ *   score     in double from T, for m < M and l < count: row[m] = sum over l < L of T[m][l] (weight on still-unlabelled
+ *             Gaussians, column L, does not count against a mask), rowall[m] the same with column L, col[l] = sum over
+ *             m <= M of T[m][l] (an instance's weight that no mask covers does count),
+ *             iou[m][l] = T[m][l] / ((row[m] + col[l]) - T[m][l]), 0 where the denominator is 0
+ *   match     best_label[m] = the lowest l of the largest iou[m][.], -1 when that is 0; best_iou[m] that value (M doubles).  m
+ *             claims best_label[m] if best_iou[m] >= iou_thresh; an instance accepts its claimant of largest IoU, the lowest m
+ *             among equals: mapping[m] = l
+ *   new       every other m with rowall[m] > min_weight takes count, count + 1, ... in ascending m while ids remain below L;
+ *             those left over get mapping[m] = -1 and are counted in `dropped`; a mask with rowall[m] <= min_weight gets -1
+ *             and is not counted.  The first view (count = 0) is no special case: every mask is new.
+ * `scratch`: f3dgs_instance_scratch_bytes(M, L) bytes, 16-byte aligned, uninitialised.  Six launches on `stream` (the table is
+ * cleared by a kernel), no host read, no memset, no allocation: capturable.  P == 0 (acc_view and acc may then be NULL): one
+ * launch that writes the outputs of an empty table - T = 0, every mask unmatched, count and dropped as they were.
+ * f3dgs_instance_merge.  For every Gaussian with acc_view[g][M] > 0: acc[g][mapping[m]] += acc_view[g][m] for every m whose
+ * mapping[m] lies in [0, L) (any other entry is ignored), and acc[g][L] += acc_view[g][M].  `mapping` (M int32, device) is
+ * associate's or the caller's own; it may repeat a target (two masks joined by hand), then both are added.  An injective mapping
+ * gives one plain fp32 add per element: the bits of acc + acc_view; with repeated targets the adds of a row are float atomics.
+ * clear_view != 0: the elements of acc_view that were read as non-zero (the total included) are written back as zeros, so that
+ * the buffer a vote filled is all zero again for the next view's vote without a memset of the whole of it.  One launch.
+ * F3DGS_ERR_INVALID_ARGUMENT, before any device work: P < 0, M outside 1 .. F3DGS_INSTANCE_MAX_MASKS, L outside
+ * 1 .. F3DGS_INSTANCE_MAX_INSTANCES, a NULL pointer (acc_view / acc only while P > 0), a misaligned scratch, an iou_thresh or
+ * min_weight that is negative or NaN.
+ */
+#define F3DGS_INSTANCE_MAX_MASKS 1024
+#define F3DGS_INSTANCE_MAX_INSTANCES 4096
+size_t f3dgs_instance_scratch_bytes(int M, int L);
+int f3dgs_instance_associate(int P, int M, int L, const float* acc_view /* P x (M + 1) */, const float* acc /* P x (L + 1) */,
+                             double iou_thresh, double min_weight, int32_t* count, int32_t* dropped, int32_t* mapping /* M */,
+                             int32_t* best_label /* M */, double* best_iou /* M */, float* table /* (M + 1) x (L + 1) */,
+                             void* scratch, void* stream /* hipStream_t */);
+int f3dgs_instance_merge(int P, int M, int L, float* acc_view /* P x (M + 1) */, int clear_view, const int32_t* mapping /* M */,
+                         float* acc /* P x (L + 1), ADDED TO */, void* stream /* hipStream_t */);
+
+/*
  * Forward-only counterpart (the inference side, render.py:169-171, :137-139, :294-296): the rendered feature map (C,H,W)
  * is resized (bilinear, align_corners=True) to (Hg,Wg) and - if weight / bias are given - decoded by the 1x1 conv into
  * `out` (Cout,Hg,Wg), fp32 or (out_is_half != 0) IEEE fp16 as render.py stores it.  Without a decoder Cout must equal C.
