@@ -2,7 +2,7 @@
 
   csrc/libf3dgs_hip.so                      the C-ABI product library (hipcc, hand-written HIP kernels)
   diff_gaussian_rasterization/_C*.so        pybind11/libtorch binding over the C ABI (g++)
-  simple_knn/_C*.so                         same, for distCUDA2
+  simple_knn/_C*.so                         same, for distCUDA2 and the neighbour lists of neighbors.py
 
 Both are written next to their sources so that they travel with a `gpurun` snapshot.  hipcc
 cross-compiles for gfx950 without a GPU.  Run:  python feature-3dgs_amd/build.py [--force]

@@ -305,6 +305,7 @@ const OptionDesc kOptions[] = {
     {"sort_onesweep", "F3DGS_SORT_ONESWEEP", &Options::sort_onesweep, 0},
     {"sync_free", "F3DGS_SYNC_FREE", &Options::sync_free, -1},
     {"instance_capacity", "F3DGS_INSTANCE_CAPACITY", &Options::instance_capacity, 0},
+    {"knn_outward", "F3DGS_KNN_OUTWARD", &Options::knn_outward, 1},
 #ifdef F3DGS_DEV
     {"dev", "F3DGS_DEV_BITS", &Options::dev, 0},
 #endif
@@ -417,7 +418,7 @@ CountReadback* count_readback(hipStream_t s, bool may_create) {
 
 extern "C" {
 
-int f3dgs_version(void) { return 31700; }   // 3.17.0 (major * 10000 + minor * 100 + patch): 3.17 f3dgs_instance_associate, f3dgs_instance_merge; 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
+int f3dgs_version(void) { return 31800; }   // 3.18.0 (major * 10000 + minor * 100 + patch): 3.18 f3dgs_knn_neighbors, f3dgs_label_mode_filter, option knn_outward; 3.17 f3dgs_instance_associate, f3dgs_instance_merge; 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
 
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 
@@ -1162,6 +1163,41 @@ int f3dgs_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* sc
     if (!points || !mean_dist2 || !scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
     launch_knn_mean_dist2(P, points, mean_dist2, static_cast<char*>(scratch), static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+size_t f3dgs_knn_neighbors_scratch_bytes(int P, int K) {
+    (void)K;      // the lists live in registers: the scratch is the front end's (sort buffers, sorted points, leaf boxes)
+    return knn_scratch_bytes((size_t)(P > 0 ? P : 0));
+}
+
+int f3dgs_knn_neighbors(int P, int K, const float* points, int32_t* idx, float* dist2, void* scratch, void* stream) {
+    const char* who = "f3dgs_knn_neighbors";
+    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
+    if (K < 1 || K > F3DGS_KNN_MAX_NEIGHBORS)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: K = %d neighbours, 1 .. %d are taken", who, K, F3DGS_KNN_MAX_NEIGHBORS);
+    if (P == 0) return F3DGS_OK;
+    if (P > (1 << 30)) return fail(F3DGS_ERR_UNSUPPORTED, "%s: more than 2^30 points", who);
+    if (!points || !idx || !scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (!aligned16(scratch)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+    HIP_TRY(launch_knn_neighbors(P, K, points, idx, dist2, static_cast<char*>(scratch), options().knn_outward != 0,
+                                 static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_label_mode_filter(int P, int K, const int32_t* labels, const float* weight, const int32_t* idx, const float* dist2,
+                            float max_dist2, int fill, int32_t* labels_out, float* share_out, void* stream) {
+    const char* who = "f3dgs_label_mode_filter";
+    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
+    if (K < 1 || K > F3DGS_KNN_MAX_NEIGHBORS)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: K = %d neighbours, 1 .. %d are taken", who, K, F3DGS_KNN_MAX_NEIGHBORS);
+    if (!(max_dist2 >= 0.f)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: max_dist2 is negative or NaN", who);
+    if (P == 0) return F3DGS_OK;
+    if (!labels || !idx || !labels_out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (labels_out == labels) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: labels_out is labels: a Jacobi step cannot run in place", who);
+    if (max_dist2 < INFINITY && !dist2) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: a finite max_dist2 needs dist2", who);
+    HIP_TRY(launch_label_mode_filter(P, K, labels, weight, idx, dist2, max_dist2, fill != 0, labels_out, share_out,
+                                     static_cast<hipStream_t>(stream)));
     return F3DGS_OK;
 }
 

@@ -233,6 +233,7 @@ struct Options {
     int sort_onesweep;   // 1: single-pass radix passes with decoupled look-back (measured slower on MI355X; default 0)
     int sync_free;       // -1 (default): as 1 inside a graph capture, as 0 otherwise; 1: the forward call never waits for the instance count in the middle of its enqueue - binning buffers of a CAPACITY, kernels that read the count on the device, the count checked behind the last launch (one retry) - and can be captured in a HIP graph; 0: the blocking read, capture refused
     int instance_capacity;   // sync_free: entries of the instance lists to provide for (0, default: 1.25 x the thread's last count on the device + 4096)
+    int knn_outward;     // f3dgs_knn_neighbors: 1: the leaves are walked outward from the wave's own (home - 1, home + 1, home - 2, ...); 0: in order.  Same result
 #ifdef F3DGS_DEV
     int dev;             // development builds only (make DEV=1): work-skipping experiments, never in a release library
 #endif
@@ -381,8 +382,20 @@ void launch_densify_gather(size_t n_out, const int32_t* src_row, const uint8_t* 
                            const DensifyTensor* tensors, hipStream_t s);
 
 // knn.hip
+constexpr int KNN_LEAF = 256;        // sorted points per leaf
+struct KnnBox {
+    float lo[3], hi[3];
+};
 size_t knn_scratch_bytes(size_t P);
+// The front end of every search: bounds, 30-bit Morton codes, the radix sort, the gather.  *sorted (P x {x, y, z, original index
+// as bits}, Morton order) and *leaf_box (*n_leaf = ceil(P / KNN_LEAF) boxes) point into `scratch` (knn_scratch_bytes(P), P >= 1).
+void launch_knn_sort(int P, const float* points, char* scratch, float4** sorted, KnnBox** leaf_box, int* n_leaf, hipStream_t s);
 void launch_knn_mean_dist2(int P, const float* points, float* out, char* scratch, hipStream_t s);
+// neighbors.hip (built with -ffp-contract=off): the K nearest neighbours with indices (f3dgs_knn_neighbors; scratch as above;
+// `outward`: option knn_outward) and the mode filter over them (f3dgs_label_mode_filter)
+hipError_t launch_knn_neighbors(int P, int K, const float* points, int* idx, float* dist2, char* scratch, bool outward, hipStream_t s);
+hipError_t launch_label_mode_filter(int P, int K, const int* labels, const float* weight, const int* idx, const float* dist2,
+                                    float max_dist2, bool fill, int* labels_out, float* share_out, hipStream_t s);
 
 // render_fwd.hip / render_bwd.hip
 // `tile_len` (zero-filled by the caller): receives the longest walk of every tile (max n_contrib of its pixels)

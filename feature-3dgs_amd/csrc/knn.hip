@@ -16,6 +16,7 @@
 //      from its own leaf, then walks all leaves: a leaf is visited if ANY lane's current third-best distance reaches
 //      its box (wave-uniform ballot, so the leaf's points are read once per wave as broadcasts), and inside a visited
 //      leaf every lane keeps its own running best three.                     (knn_query_kernel)
+// Steps 1 - 4 are launch_knn_sort, which neighbors.hip (the K nearest neighbours WITH indices) starts from as well.
 
 #include <float.h>
 
@@ -25,11 +26,8 @@ namespace f3dgs {
 
 namespace {
 
-constexpr int LEAF = 256;
-
-struct Box {
-    float lo[3], hi[3];
-};
+constexpr int LEAF = KNN_LEAF;
+using Box = KnnBox;      // (common.h: neighbors.hip reads the leaves too)
 
 __device__ __forceinline__ uint32_t spread10(uint32_t x) {   // 10 bits -> every third bit
     x = (x | (x << 16)) & 0x030000FFu;
@@ -198,7 +196,7 @@ size_t knn_scratch_bytes(size_t P) {
     return c.total();
 }
 
-void launch_knn_mean_dist2(int P, const float* points, float* out, char* scratch, hipStream_t s) {
+void launch_knn_sort(int P, const float* points, char* scratch, float4** sorted_out, KnnBox** leaf_box_out, int* n_leaf_out, hipStream_t s) {
     Carver c(scratch);
     Box* partial = c.take<Box>(1024);
     uint32_t* codes = c.take<uint32_t>(P);
@@ -216,6 +214,16 @@ void launch_knn_mean_dist2(int P, const float* points, float* out, char* scratch
     // 30-bit codes: four 8-bit passes; ids start as the index order -> equal codes keep ascending index
     launch_radix_sort_keys_to_order(codes, key_a, val_a, key_b, val_b, (size_t)P, 30, hist, s);
     hipLaunchKernelGGL(knn_gather_kernel, dim3(n_leaf), dim3(LEAF), 0, s, P, points, val_a, sorted, leaf_box);
+    *sorted_out = sorted;
+    *leaf_box_out = leaf_box;
+    *n_leaf_out = n_leaf;
+}
+
+void launch_knn_mean_dist2(int P, const float* points, float* out, char* scratch, hipStream_t s) {
+    float4* sorted;
+    Box* leaf_box;
+    int n_leaf;
+    launch_knn_sort(P, points, scratch, &sorted, &leaf_box, &n_leaf, s);
     hipLaunchKernelGGL(knn_query_kernel, dim3((P + 63) / 64), dim3(64), 0, s, P, sorted, leaf_box, n_leaf, out);
 }
 

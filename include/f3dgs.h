@@ -139,6 +139,8 @@ const char* f3dgs_last_error(void);
  *                    available inside a capture.
  *   "instance_capacity"  sync_free = 1: entries of the instance lists to provide for; 0 (default): 1.25 x the last count this
  *                    thread read on the device + 4096
+ *   "knn_outward"    f3dgs_knn_neighbors: 1 (default) a wave walks the leaves outward from its own (home - 1, home + 1,
+ *                    home - 2, ...), 0 in storage order; the lists are the same bits either way
  * Unknown names return F3DGS_ERR_INVALID_ARGUMENT.
  */
 int f3dgs_set_option(const char* name, int value);
@@ -879,6 +881,40 @@ int f3dgs_densify_gather(size_t n_out, const int32_t* src_row, const uint8_t* ki
  */
 size_t f3dgs_knn_scratch_bytes(int P);
 int f3dgs_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* scratch, void* stream /* hipStream_t */);
+
+/*
+ * The K nearest neighbours of every point WITH their indices (no counterpart in the reference, whose search returns the mean
+ * distance alone), exact and uniquely defined.  points (P, 3), idx (P, K) int32, dist2 (P, K) float32 or NULL: device pointers.
+ * 1 <= K <= F3DGS_KNN_MAX_NEIGHBORS.  Row i holds the K points j != i with the smallest (dist2, j) in LEXICOGRAPHIC order:
+ * ascending distance, among equal distances the lower index.  Self is excluded by index, not by distance: a duplicate of
+ * point i is its neighbour at distance 0.  Every distance is ((dx*dx) + (dy*dy)) + (dz*dz) with dx = candidate - query in
+ * float32, one rounding per operation, so the result is a function of the inputs alone (not of the sort order, the walk order or
+ * the lanes).  A slot without a neighbour (P - 1 < K) holds idx = -1 and dist2 = FLT_MAX, f3dgs_knn_mean_dist2's convention.  A
+ * point with a NaN or infinite coordinate is nobody's neighbour and has none (its row is all -1); a pair whose distance
+ * overflows float32 (is not < inf) is no neighbour pair either.
+ * `scratch` = f3dgs_knn_neighbors_scratch_bytes(P, K) bytes of device memory, 16-byte aligned.  P == 0 is a no-op.  P < 0, K
+ * out of range, a NULL points / idx / scratch, a misaligned scratch: F3DGS_ERR_INVALID_ARGUMENT before any device work; P > 2^30:
+ * F3DGS_ERR_UNSUPPORTED.  No host read, no allocation, no memset; every launch goes to `stream`: capturable.
+ *
+ * f3dgs_label_mode_filter: one Jacobi step of a weighted mode filter of per-point labels over such lists, ONE launch.  labels
+ * (P) int32 (negative: unlabelled; any non-negative value is a label), weight (P) float32 or NULL (1 each), idx (P, K) - the
+ * caller's, every entry is bounds-checked -, dist2 (P, K) or NULL, labels_out (P) int32, share_out (P) float32 or NULL.
+ * Voters of point i, in this order: i itself, then idx[i, 0 .. K-1].  Voter j votes iff 0 <= j < P, labels[j] >= 0, its weight
+ * w > 0 && w < inf, and - for a neighbour - dist2[i, slot] <= max_dist2 (max_dist2 = +inf: no limit, dist2 is not read; a finite
+ * max_dist2 with a NULL dist2, a negative or NaN max_dist2: F3DGS_ERR_INVALID_ARGUMENT).  The score of a label is the float32
+ * sum of its voters' weights taken in voter order.  The largest score wins; among equal scores labels[i] if it is one of them
+ * (whether or not i itself voted), otherwise the smallest label.  labels_out[i] = the winner, -1 with no voter; with fill == 0
+ * a point whose own label is negative stays -1.  share_out[i] = the winner's score over the voters' total, one IEEE division; 0
+ * where labels_out[i] is -1.  labels_out == labels is refused (F3DGS_ERR_INVALID_ARGUMENT): the step reads the OLD labels
+ * only.  A pure function of its inputs: two calls give the same bits.  Capturable like the search.
+ */
+#define F3DGS_KNN_MAX_NEIGHBORS 16
+size_t f3dgs_knn_neighbors_scratch_bytes(int P, int K);
+int f3dgs_knn_neighbors(int P, int K, const float* points, int32_t* idx, float* dist2 /* or NULL */, void* scratch,
+                        void* stream /* hipStream_t */);
+int f3dgs_label_mode_filter(int P, int K, const int32_t* labels, const float* weight /* or NULL */, const int32_t* idx,
+                            const float* dist2 /* or NULL */, float max_dist2, int fill, int32_t* labels_out,
+                            float* share_out /* or NULL */, void* stream /* hipStream_t */);
 
 /*
  * ---- Side channels of f3dgs_backward: threading contract -----------------------------------------------------------
