@@ -4,6 +4,8 @@
 // Beside it, with no counterpart in the reference (neighbors.py is their Python surface):
 //   knn_neighbors(points, K, want_dist2) -> (idx (P,K) int32, dist2 (P,K) float32 or None): f3dgs_knn_neighbors
 //   label_mode_filter(labels, weight, idx, dist2, max_dist2, fill, labels_out, share_out): one step of f3dgs_label_mode_filter
+//   knn_components(idx, dist2, max_dist2, labels, mutual, dense) -> (root, size, comp, comp_root, n_comp, status): f3dgs_knn_components
+//   component_filter(labels, root, size, min_size, largest, num_labels, labels_out): f3dgs_component_filter
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/extension.h>
@@ -83,11 +85,72 @@ void label_mode_filter(const torch::Tensor& labels, const c10::optional<torch::T
     if (rc != F3DGS_OK) throw std::runtime_error(std::string("label_mode_filter: ") + f3dgs_last_error());
 }
 
+void check_node_array(const torch::Tensor& t, long long P, const torch::Device& dev, const char* name) {
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == P && t.scalar_type() == torch::kInt32 && t.device() == dev && t.is_contiguous(), name,
+                ": contiguous int32 (P) on the lists' device expected");
+}
+
+// f3dgs_knn_components: (root, size, comp, comp_root, n_comp, status), all int32; comp, comp_root (P) and n_comp (a 0-dim tensor)
+// only with `dense`; status a 0-dim tensor.  Nothing is read back.
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, torch::Tensor>
+knn_components(const torch::Tensor& idx, const c10::optional<torch::Tensor>& dist2, double max_dist2,
+               const c10::optional<torch::Tensor>& labels, bool mutual, bool dense) {
+    TORCH_CHECK(idx.is_cuda(), "idx must live on a HIP device: the components have no CPU path");
+    TORCH_CHECK(idx.dim() == 2 && idx.scalar_type() == torch::kInt32 && idx.is_contiguous(), "idx: contiguous int32 (P, K) expected");
+    TORCH_CHECK(idx.size(0) <= (1ll << 30), "too many points");
+    const long long P = idx.size(0);
+    const int K = (int)idx.size(1);
+    if (dist2) TORCH_CHECK(dist2->sizes() == idx.sizes() && dist2->scalar_type() == torch::kFloat32 && dist2->device() == idx.device() &&
+                               dist2->is_contiguous(), "dist2: contiguous float32 (P, K) on the lists' device expected");
+    if (labels) check_node_array(*labels, P, idx.device(), "labels");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(idx.device());
+    const auto ints = idx.options();
+    torch::Tensor root = torch::empty({P}, ints), size = torch::empty({P}, ints), status = torch::empty({}, ints);
+    c10::optional<torch::Tensor> comp, comp_root, n_comp;
+    torch::Tensor scratch;
+    if (dense) {
+        comp = torch::empty({P}, ints);
+        comp_root = torch::empty({P}, ints);
+        n_comp = torch::empty({}, ints);
+        scratch = torch::empty({(long long)f3dgs_knn_components_scratch_bytes((int)P, 0)}, ints.dtype(torch::kByte));
+    }
+    const int rc = f3dgs_knn_components((int)P, K, idx.data_ptr<int32_t>(), dist2 ? dist2->data_ptr<float>() : nullptr, (float)max_dist2,
+                                        labels ? labels->data_ptr<int32_t>() : nullptr, mutual ? 1 : 0, root.data_ptr<int32_t>(),
+                                        size.data_ptr<int32_t>(), dense ? comp->data_ptr<int32_t>() : nullptr,
+                                        dense ? comp_root->data_ptr<int32_t>() : nullptr, dense ? n_comp->data_ptr<int32_t>() : nullptr,
+                                        status.data_ptr<int32_t>(), dense ? scratch.data_ptr() : nullptr, current_stream(idx));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("knn_components: ") + f3dgs_last_error());
+    return {root, size, comp, comp_root, n_comp, status};
+}
+
+// f3dgs_component_filter into the caller's labels_out (which may be labels)
+void component_filter(const c10::optional<torch::Tensor>& labels, const torch::Tensor& root, const torch::Tensor& size, int min_size,
+                      bool largest, int num_labels, torch::Tensor& labels_out) {
+    TORCH_CHECK(root.is_cuda(), "root must live on a HIP device: the component filter has no CPU path");
+    TORCH_CHECK(root.dim() == 1, "root: contiguous int32 (P) expected");
+    const long long P = root.size(0);
+    TORCH_CHECK(P <= (1ll << 30), "too many points");
+    check_node_array(root, P, root.device(), "root");
+    check_node_array(size, P, root.device(), "size");
+    check_node_array(labels_out, P, root.device(), "labels_out");
+    if (labels) check_node_array(*labels, P, root.device(), "labels");
+    TORCH_CHECK(!largest || num_labels >= 0, "num_labels = ", num_labels, " with largest");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(root.device());
+    torch::Tensor scratch;
+    if (largest) scratch = torch::empty({(long long)f3dgs_knn_components_scratch_bytes(0, num_labels)}, root.options().dtype(torch::kByte));
+    const int rc = f3dgs_component_filter((int)P, labels ? labels->data_ptr<int32_t>() : nullptr, root.data_ptr<int32_t>(),
+                                          size.data_ptr<int32_t>(), min_size, largest ? 1 : 0, num_labels, labels_out.data_ptr<int32_t>(),
+                                          largest ? scratch.data_ptr() : nullptr, current_stream(root));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("component_filter: ") + f3dgs_last_error());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
     m.def("distCUDA2", &distCUDA2);
     m.def("knn_neighbors", &knn_neighbors);
     m.def("label_mode_filter", &label_mode_filter);
+    m.def("knn_components", &knn_components);
+    m.def("component_filter", &component_filter);
     m.attr("KNN_MAX_NEIGHBORS") = F3DGS_KNN_MAX_NEIGHBORS;
 }

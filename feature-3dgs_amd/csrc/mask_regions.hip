@@ -13,6 +13,7 @@
 //                           every touching pair.  A union links the LARGER root to the smaller by compare-and-swap: a parent is
 //                           only ever lowered, a walk to the root visits strictly decreasing indices, and the root of a
 //                           component is its smallest run.  Agent-scope atomics on both sides: other workgroups' links are seen.
+//                           (find_root and unite live in union_find.h, shared with components.hip.)
 //   regions_flatten_kernel  every run finds its root, points at it, and adds its area / lowers the root's key (integer atomics)
 //   regions_decide_kernel   every root: the mask's components, its small ones, and the largest (ties: the smallest key) by one
 //                           64-bit atomicMax of size << 32 | ~key
@@ -26,6 +27,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "union_find.h"
 
 namespace f3dgs {
 
@@ -75,8 +77,6 @@ __device__ __forceinline__ long long total_runs(const int32_t* hdr) { return *re
 
 __device__ __forceinline__ int col_begin(const Runs& r, const Shape& s, int k, int x) { return r.base[k] + r.local[(size_t)k * s.FW + x]; }
 __device__ __forceinline__ int col_end(const Runs& r, const Shape& s, int k, int x) { return x + 1 < s.FW ? col_begin(r, s, k, x + 1) : r.base[k + 1]; }
-
-__device__ __forceinline__ int32_t load_agent(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // exclusive prefix of v over the 256 threads, and the sum
 template <typename T>
@@ -182,40 +182,6 @@ __global__ void __launch_bounds__(256) regions_emit_kernel(Shape s, const uint32
         prev = v >> 31;
         v = next;
     }
-}
-
-// the root of run i: parents only decrease, so the walk ends; `cap` (the number of runs) bounds it besides.  Path halving by
-// atomicMin keeps "a parent is only lowered".
-__device__ __forceinline__ int find_root(int32_t* parent, int i, int cap, int32_t* err) {
-    int p = load_agent(parent + i);
-    for (int it = 0; p != i; it++) {
-        if (it >= cap || p > i) {
-            atomicOr(err, 1);
-            return -1;
-        }
-        const int g = load_agent(parent + p);
-        if (g != p) atomicMin(parent + i, g);
-        i = p;
-        p = g;
-    }
-    return i;
-}
-
-__device__ __forceinline__ void unite(int32_t* parent, int a, int b, int cap, int32_t* err) {
-    for (int it = 0; it <= cap; it++) {
-        a = find_root(parent, a, cap, err);
-        b = find_root(parent, b, cap, err);
-        if (a < 0 || b < 0 || a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicCAS(parent + a, a, b);                       // the larger root under the smaller
-        if (old == a) return;
-        a = old;                                                           // another link came first: go on from where it points
-    }
-    atomicOr(err, 2);
 }
 
 __global__ void __launch_bounds__(256) regions_link_kernel(Shape s, Runs r) {

@@ -10,14 +10,26 @@ Gaussian's neighbours (csrc/neighbors.hip behind include/f3dgs.h: f3dgs_knn_neig
     smooth_labels    mode_filter over a LabelLifter's / InstanceLifter's labels(), weighted with confidence()
     clean_selection  the same filter on a boolean `mask` of edit.apply_edit: drops isolated selected Gaussians, fills pinholes
 
+A vote is local.  The lists as a GRAPH (csrc/components.hip: f3dgs_knn_components, f3dgs_component_filter) answer what comes after
+a selection exists:
+
+    components       the connected components over the lists: per Gaussian the smallest index and the size of its component,
+                     on request dense ids; edges join equal labels only, within max_dist, on request mutual neighbours only
+    drop_small       labels or a bool mask without the connected parts below min_size Gaussians (the floaters)
+    keep_largest     of every label only its largest connected part
+    split_labels     every connected part of a label an id of its own: one instance id with two bodies becomes two ids
+
     idx, dist2 = neighbors.knn(gaussians.get_xyz.detach(), 8)
     labels = neighbors.smooth_labels(lifter, gaussians.get_xyz.detach(), k=8, iterations=2)
     mask = neighbors.clean_selection(lifter.select(cls), idx)
+    mask = neighbors.keep_largest(mask, idx)
+    ids = neighbors.split_labels(instance_lifter.labels(), idx, dist2=dist2, max_dist=0.1).comp
 
 HIP only; no CPU fallback.  Nothing is read back to the host.
 """
 from __future__ import annotations
 
+import collections
 import math
 
 import torch
@@ -138,4 +150,96 @@ def clean_selection(mask, idx, weight=None, dist2=None, max_dist=None, iteration
     return out == 1
 
 
-__all__ = ["MAX_NEIGHBORS", "knn", "mode_filter", "smooth_labels", "clean_selection"]
+# ---- the lists as a graph: connected components ----------------------------------------------------------------------------
+
+Components = collections.namedtuple("Components", ["root", "size", "comp", "comp_root", "n_comp", "status"])
+SplitLabels = collections.namedtuple("SplitLabels", ["comp", "n_comp", "comp_label"])
+
+
+def _int_labels(labels, idx, name="labels"):
+    """labels as the kernels take them: int32, contiguous, every negative value -1"""
+    _need_device(labels, name)
+    if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: an int32 or int64 (P,) tensor expected, got {_describe(labels)}")
+    _check_lists(idx, None, labels.shape[0], labels.device)
+    return labels.detach().clamp_min(-1).to(torch.int32).contiguous()
+
+
+def _components(idx, labels32, dist2, max_dist, mutual, dense):
+    """the int32 tensors of _C.knn_components; labels32: _int_labels' or None"""
+    _need_device(idx, "idx")
+    _check_lists(idx, dist2, idx.shape[0] if idx.dim() else -1, idx.device)
+    limit2 = _max_dist2(max_dist, dist2)
+    d2 = None if (dist2 is None or math.isinf(limit2)) else dist2.detach().contiguous()
+    with torch.no_grad():
+        return _C.knn_components(idx.contiguous(), d2, limit2, labels32, bool(mutual), bool(dense))
+
+
+def components(idx, labels=None, dist2=None, max_dist=None, mutual=False, dense=False):
+    """The connected components of the Gaussians over their neighbour lists.  idx (P, K) int32 and dist2 (P, K) float32: knn's
+    lists (any integers are allowed in idx: an entry outside 0 .. P-1 or equal to its row is no edge).  labels: (P,) int32 or
+    int64 or None; a negative label takes its Gaussian out of the graph (root -1, size 0, comp -1), and an edge joins equal labels
+    only.  max_dist: an edge needs dist2[i, slot] <= max_dist^2 (None: no limit).  {i, j} is an edge if j is in i's list or i in
+    j's; with mutual=True only if both.
+
+    Returns Components(root, size, comp, comp_root, n_comp, status), int64 like LabelLifter.labels(): root[i] the smallest index
+    of i's component, size[i] its number of members; with dense=True also comp[i] (the rank of root[i] among the roots),
+    comp_root (P,) (the root of component c for c < n_comp, -1 behind) and n_comp (a 0-dim tensor on the device, never read here);
+    without, the three are None.  status: a 0-dim device tensor, 0 (non-zero only if a union-find walk reached its cap)."""
+    labels32 = None if labels is None else _int_labels(labels, idx)
+    res = _components(idx, labels32, dist2, max_dist, mutual, dense)
+    return Components(*(None if t is None else t.long() for t in res))
+
+
+def _filter_components(labels_or_mask, idx, min_size, largest, num_labels, dist2, max_dist, mutual):
+    if not isinstance(min_size, int) or isinstance(min_size, bool) or not 1 <= min_size < 2**31:
+        raise ValueError(f"min_size = {min_size!r}: an integer >= 1 expected")
+    _need_device(labels_or_mask, "labels")
+    is_mask = labels_or_mask.dtype == torch.bool
+    if is_mask:
+        if labels_or_mask.dim() != 1:
+            raise ValueError(f"mask: a bool (P,) tensor expected, got {_describe(labels_or_mask)}")
+        _check_lists(idx, None, labels_or_mask.shape[0], labels_or_mask.device)
+        labels32 = labels_or_mask.to(torch.int32) - 1             # selected: label 0, unselected: -1
+        num_labels = 1
+    else:
+        labels32 = _int_labels(labels_or_mask, idx)               # a new tensor: filtered in place below
+        if largest and (not isinstance(num_labels, int) or isinstance(num_labels, bool) or not 0 <= num_labels < 2**31):
+            raise ValueError(f"num_labels = {num_labels!r}: keep_largest on labels needs the number of labels (a lifter's class count "
+                             f"or max_instances), an integer >= 0")
+    root, size = _components(idx, labels32, dist2, max_dist, mutual, False)[:2]
+    with torch.no_grad():
+        _C.component_filter(labels32, root, size, min_size, bool(largest), num_labels if largest else 0, labels32)
+    return labels32 >= 0 if is_mask else labels32.long()
+
+
+def drop_small(labels_or_mask, idx, min_size, dist2=None, max_dist=None, mutual=False):
+    """Drops the connected parts below min_size Gaussians.  labels_or_mask: (P,) int32 / int64 labels (negative = unlabelled; a
+    component joins equal labels only) or a bool `mask` of edit.apply_edit (selected = label 0).  Returns the labels as int64 with
+    -1 where a part was dropped, or the mask as bool.  idx, dist2, max_dist, mutual: as for components()."""
+    return _filter_components(labels_or_mask, idx, min_size, False, None, dist2, max_dist, mutual)
+
+
+def keep_largest(labels_or_mask, idx, num_labels=None, min_size=1, dist2=None, max_dist=None, mutual=False):
+    """Keeps, of every label, its largest connected part (among equal sizes the one that holds the lowest index) if it has
+    min_size Gaussians; everything else becomes -1 (False for a bool mask).  On labels num_labels is needed - a lifter's class
+    count or max_instances -, and a label >= num_labels is dropped; a bool mask needs none."""
+    return _filter_components(labels_or_mask, idx, min_size, True, num_labels, dist2, max_dist, mutual)
+
+
+def split_labels(labels, idx, dist2=None, max_dist=None, mutual=False):
+    """Re-ids a label field whose ids have several bodies (an InstanceLifter's, where two chairs shared a mask): every connected
+    part of a label becomes an id of its own.  Returns SplitLabels(comp, n_comp, comp_label): comp (P,) int64, the new id of every
+    Gaussian (-1 where labels is negative), ascending in the parts' lowest index; n_comp, their number, a 0-dim device tensor;
+    comp_label (P,) int64, the old label of id c for c < n_comp and -1 behind."""
+    labels32 = _int_labels(labels, idx)
+    _, _, comp, comp_root, n_comp, _ = _components(idx, labels32, dist2, max_dist, mutual, True)
+    with torch.no_grad():
+        comp_root = comp_root.long()
+        old = labels32.long().gather(0, comp_root.clamp_min(0)) if labels32.shape[0] else labels32.long()
+        comp_label = torch.where(comp_root >= 0, old, torch.full((), -1, dtype=torch.int64, device=old.device))
+    return SplitLabels(comp.long(), n_comp.long(), comp_label)
+
+
+__all__ = ["MAX_NEIGHBORS", "knn", "mode_filter", "smooth_labels", "clean_selection", "Components", "SplitLabels", "components",
+           "drop_small", "keep_largest", "split_labels"]

@@ -917,6 +917,53 @@ int f3dgs_label_mode_filter(int P, int K, const int32_t* labels, const float* we
                             float* share_out /* or NULL */, void* stream /* hipStream_t */);
 
 /*
+ * Connected components of the points over such lists (ABI 3.19; no counterpart in the reference): the lists as a graph.
+ * idx (P, K) int32 - the caller's: any integers, every entry is bounds-checked -, dist2 (P, K) float32 or NULL, labels (P) int32
+ * or NULL: device pointers.  1 <= K <= F3DGS_KNN_MAX_NEIGHBORS.
+ *   Active nodes   node i is active iff labels == NULL or labels[i] >= 0; with labels == NULL every node carries label 0.  An
+ *                  inactive node gets root = -1, size = 0, comp = -1.
+ *   Directed edge  slot s of row i is an edge i -> j, j = idx[i, s], when 0 <= j < P and j != i, both ends are active and carry the
+ *                  same label, and - when max_dist2 < inf - dist2[i, s] <= max_dist2 (a NaN distance gives no edge:
+ *                  f3dgs_label_mode_filter's comparison).  A finite max_dist2 with a NULL dist2, a negative or NaN max_dist2:
+ *                  F3DGS_ERR_INVALID_ARGUMENT.
+ *   Graph          undirected.  mutual == 0: {i, j} is an edge iff i -> j or j -> i.  mutual != 0: iff both, each direction judged
+ *                  on its own slot (K more reads per edge, done only when asked).
+ *   root, size     (P) int32: root[i] is the smallest index of i's component, size[i] the number of its members - for every member.
+ *   comp, comp_root, n_comp   the dense ids, written only when comp is not NULL (comp_root, n_comp and scratch are needed then):
+ *                  n_comp (one int32 on the device) the number of components, comp[i] the rank of root[i] among the roots in
+ *                  ascending order, comp_root[c] the root of component c for c < n_comp and -1 for n_comp <= c < P.
+ *   status         one int32 on the device, always written: 0, non-zero only if a walk of the union-find reached its cap of P steps
+ *                  (it cannot, by construction).  This function does not read it.
+ * `scratch` = f3dgs_knn_components_scratch_bytes(P, num_labels) bytes of device memory, 8-byte aligned; the same size serves
+ * f3dgs_component_filter (num_labels is its table; 0 for this call alone).  P == 0 is a no-op apart from n_comp = 0 (where given) and
+ * status = 0.  P < 0, K out of range, a NULL idx / root / size / status, root == size (or any two outputs the same array):
+ * F3DGS_ERR_INVALID_ARGUMENT before any device work; P > 2^30: F3DGS_ERR_UNSUPPORTED.  One launch per stage (init, link, flatten and
+ * count, spread; for the dense ids a three-launch exclusive prefix over P and one more launch), no workgroup waits for another, no
+ * host read, no allocation, no memset node: capturable as one linear graph.  Integers only: two calls give the same bits.
+ *
+ * f3dgs_component_filter: labels_out[i] = labels[i] (0 for NULL labels) iff i is active, size[i] >= min_size and - with largest !=
+ * 0 - i's component is the best of its label: the largest size, among equal sizes the smallest root; a label >= num_labels is
+ * nobody's best.  Otherwise labels_out[i] = -1.  root and size are f3dgs_knn_components' for the same labels.  num_labels is used
+ * only with largest (a table of num_labels 64-bit words in `scratch`, cleared by a launch; scratch may be NULL without largest).
+ * labels_out == labels is allowed: the filter is elementwise in i.  Three launches with largest, one without; capturable.
+ *
+ * f3dgs_debug_knn_components_shape: f3dgs_knn_components without the dense ids, with the link stage as named - 0: one thread per
+ * node, its row in registers; 1: one thread per (node, slot) (what f3dgs_knn_components runs); 2: no link at all, every active
+ * node a component (the floor of the other stages).  The same results for 0 and 1.  For measurements and tests.
+ */
+size_t f3dgs_knn_components_scratch_bytes(int P, int num_labels);
+int f3dgs_knn_components(int P, int K, const int32_t* idx, const float* dist2 /* or NULL */, float max_dist2,
+                         const int32_t* labels /* or NULL */, int mutual, int32_t* root, int32_t* size, int32_t* comp /* or NULL */,
+                         int32_t* comp_root /* or NULL */, int32_t* n_comp /* device, or NULL */, int32_t* status /* device */,
+                         void* scratch, void* stream /* hipStream_t */);
+int f3dgs_component_filter(int P, const int32_t* labels /* or NULL */, const int32_t* root, const int32_t* size, int min_size,
+                           int largest, int num_labels, int32_t* labels_out, void* scratch /* or NULL */,
+                           void* stream /* hipStream_t */);
+int f3dgs_debug_knn_components_shape(int P, int K, const int32_t* idx, const float* dist2 /* or NULL */, float max_dist2,
+                                     const int32_t* labels /* or NULL */, int mutual, int shape, int32_t* root, int32_t* size,
+                                     int32_t* status /* device */, void* stream /* hipStream_t */);
+
+/*
  * ---- Side channels of f3dgs_backward: threading contract -----------------------------------------------------------
  * The four setters below and f3dgs_set_feature_grad_lowres change how the f3dgs_backward calls OF THE CALLING HOST THREAD
  * behave.  All five are thread-local: they are invisible to, and unaffected by, any other thread.
