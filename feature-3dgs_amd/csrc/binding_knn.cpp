@@ -6,12 +6,15 @@
 //   label_mode_filter(labels, weight, idx, dist2, max_dist2, fill, labels_out, share_out): one step of f3dgs_label_mode_filter
 //   knn_components(idx, dist2, max_dist2, labels, mutual, dense) -> (root, size, comp, comp_root, n_comp, status): f3dgs_knn_components
 //   component_filter(labels, root, size, min_size, largest, num_labels, labels_out): f3dgs_component_filter
+//   group_stats(groups, xyz, G, weight, features, want) -> (count, mass, centroid, cov, aabb, feature_mean), each or None: f3dgs_group_stats
+//   group_merge(groups, idx, dist2, max_dist2, mutual, feature_mean, min_cos, out) -> (groups_out, group_root, status): f3dgs_group_merge
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/extension.h>
 
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/f3dgs.h"
 
@@ -144,6 +147,97 @@ void component_filter(const c10::optional<torch::Tensor>& labels, const torch::T
     if (rc != F3DGS_OK) throw std::runtime_error(std::string("component_filter: ") + f3dgs_last_error());
 }
 
+// f3dgs_group_stats: `want` names the outputs (GROUP_COUNT ... GROUP_FEATURE_MEAN); the others come back as None.  count (G) int32,
+// mass (G), centroid (G, 3), cov (G, 6), aabb (G, 6), feature_mean (G, C) float32.  features: (P, C) float32 with unit stride along
+// C and any row stride >= C (a view is read in place).  Nothing is read back.
+enum { GROUP_COUNT = 1, GROUP_MASS = 2, GROUP_CENTROID = 4, GROUP_COV = 8, GROUP_AABB = 16, GROUP_FEATURE_MEAN = 32 };
+
+std::vector<c10::optional<torch::Tensor>> group_stats(const torch::Tensor& groups, const torch::Tensor& xyz, int G,
+                                                      const c10::optional<torch::Tensor>& weight,
+                                                      const c10::optional<torch::Tensor>& features, int want) {
+    TORCH_CHECK(groups.is_cuda(), "groups must live on a HIP device: the group statistics have no CPU path");
+    TORCH_CHECK(groups.dim() == 1 && groups.scalar_type() == torch::kInt32 && groups.is_contiguous(), "groups: contiguous int32 (P) expected");
+    const long long P = groups.size(0);
+    TORCH_CHECK(P < (1ll << 31), "too many points");
+    const auto dev = groups.device();
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(0) == P && xyz.size(1) == 3 && xyz.scalar_type() == torch::kFloat32 && xyz.device() == dev &&
+                    xyz.is_contiguous(), "xyz: contiguous float32 (P, 3) on the groups' device expected");
+    TORCH_CHECK(G >= 1 && G <= F3DGS_GROUP_MAX_GROUPS, "G = ", G, ": 1 .. ", F3DGS_GROUP_MAX_GROUPS, " groups are taken");
+    if (weight) TORCH_CHECK(weight->dim() == 1 && weight->size(0) == P && weight->scalar_type() == torch::kFloat32 && weight->device() == dev &&
+                                weight->is_contiguous(), "weight: contiguous float32 (P) on the groups' device expected");
+    int C = 0;
+    long long stride = 0;
+    if (features) {
+        TORCH_CHECK(features->dim() == 2 && features->size(0) == P && features->scalar_type() == torch::kFloat32 && features->device() == dev,
+                    "features: float32 (P, C) on the groups' device expected");
+        TORCH_CHECK(features->size(1) >= 1 && features->size(1) <= F3DGS_GROUP_MAX_CHANNELS, "C = ", features->size(1), ": 1 .. ",
+                    F3DGS_GROUP_MAX_CHANNELS, " channels are taken");
+        C = (int)features->size(1);
+        stride = P > 1 ? features->stride(0) : C;
+        TORCH_CHECK(P == 0 || ((C == 1 || features->stride(1) == 1) && stride >= C),
+                    "features: unit stride along C and a row stride >= C expected");
+    }
+    TORCH_CHECK(want > 0 && want < 64, "want = ", want, ": a sum of GROUP_COUNT ... GROUP_FEATURE_MEAN expected");
+    TORCH_CHECK(!(want & GROUP_FEATURE_MEAN) || features, "feature_mean needs features");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto floats = xyz.options();
+    std::vector<c10::optional<torch::Tensor>> out(6);
+    if (want & GROUP_COUNT) out[0] = torch::empty({G}, groups.options());
+    if (want & GROUP_MASS) out[1] = torch::empty({G}, floats);
+    if (want & GROUP_CENTROID) out[2] = torch::empty({G, 3}, floats);
+    if (want & GROUP_COV) out[3] = torch::empty({G, 6}, floats);
+    if (want & GROUP_AABB) out[4] = torch::empty({G, 6}, floats);
+    if (want & GROUP_FEATURE_MEAN) out[5] = torch::empty({G, C}, floats);
+    const size_t bytes = f3dgs_group_stats_scratch_bytes(G, C);
+    torch::Tensor scratch = torch::empty({(long long)bytes}, floats.dtype(torch::kByte));
+    auto fp = [&](int k) { return out[k] ? out[k]->data_ptr<float>() : nullptr; };
+    // (an empty tensor has no address, and C > 0 needs one: with P == 0 nothing is read through it)
+    const float* feat = !features ? nullptr : (P > 0 ? features->data_ptr<float>() : static_cast<const float*>(scratch.data_ptr()));
+    const int rc = f3dgs_group_stats((int)P, G, C, groups.data_ptr<int32_t>(), xyz.data_ptr<float>(), weight ? weight->data_ptr<float>() : nullptr,
+                                     feat, stride, out[0] ? out[0]->data_ptr<int32_t>() : nullptr,
+                                     fp(1), fp(2), fp(3), fp(4), fp(5), scratch.data_ptr(), bytes, current_stream(groups));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("group_stats: ") + f3dgs_last_error());
+    return out;
+}
+
+// f3dgs_group_merge: (groups_out (P), group_root (G), status), int32; `out`: the caller's groups_out (it may be `groups`)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> group_merge(const torch::Tensor& groups, const torch::Tensor& idx,
+                                                                    const c10::optional<torch::Tensor>& dist2, double max_dist2, bool mutual,
+                                                                    const torch::Tensor& feature_mean, double min_cos,
+                                                                    const c10::optional<torch::Tensor>& out) {
+    TORCH_CHECK(groups.is_cuda(), "groups must live on a HIP device: the merge has no CPU path");
+    TORCH_CHECK(groups.dim() == 1, "groups: contiguous int32 (P) expected");
+    const long long P = groups.size(0);
+    TORCH_CHECK(P <= (1ll << 30), "too many points");
+    const auto dev = groups.device();
+    check_node_array(groups, P, dev, "groups");
+    TORCH_CHECK(idx.dim() == 2 && idx.size(0) == P && idx.scalar_type() == torch::kInt32 && idx.device() == dev && idx.is_contiguous(),
+                "idx: contiguous int32 (P, K) on the groups' device expected");
+    const int K = (int)idx.size(1);
+    if (dist2) TORCH_CHECK(dist2->sizes() == idx.sizes() && dist2->scalar_type() == torch::kFloat32 && dist2->device() == dev &&
+                               dist2->is_contiguous(), "dist2: contiguous float32 (P, K) on the groups' device expected");
+    TORCH_CHECK(feature_mean.dim() == 2 && feature_mean.scalar_type() == torch::kFloat32 && feature_mean.device() == dev &&
+                    feature_mean.is_contiguous(), "feature_mean: contiguous float32 (G, C) on the groups' device expected");
+    TORCH_CHECK(feature_mean.size(0) >= 1 && feature_mean.size(0) <= F3DGS_GROUP_MERGE_MAX_GROUPS, "G = ", feature_mean.size(0), ": 1 .. ",
+                F3DGS_GROUP_MERGE_MAX_GROUPS, " groups are taken");
+    TORCH_CHECK(feature_mean.size(1) >= 1 && feature_mean.size(1) <= F3DGS_GROUP_MAX_CHANNELS, "C = ", feature_mean.size(1), ": 1 .. ",
+                F3DGS_GROUP_MAX_CHANNELS, " channels are taken");
+    const int G = (int)feature_mean.size(0), C = (int)feature_mean.size(1);
+    if (out) check_node_array(*out, P, dev, "out");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto ints = groups.options();
+    torch::Tensor groups_out = out ? *out : torch::empty({P}, ints);
+    torch::Tensor group_root = torch::empty({G}, ints), status = torch::empty({}, ints);
+    const size_t bytes = f3dgs_group_merge_scratch_bytes(G);
+    torch::Tensor scratch = torch::empty({(long long)bytes}, ints.dtype(torch::kByte));
+    const int rc = f3dgs_group_merge((int)P, K, G, C, groups.data_ptr<int32_t>(), idx.data_ptr<int32_t>(), dist2 ? dist2->data_ptr<float>() : nullptr,
+                                     (float)max_dist2, mutual ? 1 : 0, feature_mean.data_ptr<float>(), (float)min_cos,
+                                     group_root.data_ptr<int32_t>(), groups_out.data_ptr<int32_t>(), status.data_ptr<int32_t>(),
+                                     scratch.data_ptr(), bytes, current_stream(groups));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("group_merge: ") + f3dgs_last_error());
+    return {groups_out, group_root, status};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -152,5 +246,16 @@ PYBIND11_MODULE(_C, m) {
     m.def("label_mode_filter", &label_mode_filter);
     m.def("knn_components", &knn_components);
     m.def("component_filter", &component_filter);
+    m.def("group_stats", &group_stats);
+    m.def("group_merge", &group_merge);
+    m.attr("GROUP_COUNT") = (int)GROUP_COUNT;
+    m.attr("GROUP_MASS") = (int)GROUP_MASS;
+    m.attr("GROUP_CENTROID") = (int)GROUP_CENTROID;
+    m.attr("GROUP_COV") = (int)GROUP_COV;
+    m.attr("GROUP_AABB") = (int)GROUP_AABB;
+    m.attr("GROUP_FEATURE_MEAN") = (int)GROUP_FEATURE_MEAN;
+    m.attr("GROUP_MAX_GROUPS") = F3DGS_GROUP_MAX_GROUPS;
+    m.attr("GROUP_MAX_CHANNELS") = F3DGS_GROUP_MAX_CHANNELS;
+    m.attr("GROUP_MERGE_MAX_GROUPS") = F3DGS_GROUP_MERGE_MAX_GROUPS;
     m.attr("KNN_MAX_NEIGHBORS") = F3DGS_KNN_MAX_NEIGHBORS;
 }

@@ -964,6 +964,64 @@ int f3dgs_debug_knn_components_shape(int P, int K, const int32_t* idx, const flo
                                      int32_t* status /* device */, void* stream /* hipStream_t */);
 
 /*
+ * Statistics of the Gaussians per group id (ABI 3.20; no counterpart in the reference): what the integers of the label vote, the
+ * instance association, the mode filter and the components say about a class, an instance or a component AS A WHOLE.
+ *
+ * f3dgs_group_stats.  Gaussian i is a MEMBER of group g = groups[i] iff 0 <= g < G, its three coordinates are finite and -
+ * with weight != NULL - 0 < weight[i] < inf (the mode filter's voter rule: a NaN weight is no member).  Any integers may stand in
+ * `groups`; nothing is read or written out of bounds.  w_i = weight[i], or 1 for a NULL weight; M = sum of w over the members of g.
+ *   count         (G) int32   the number of members (exact)
+ *   mass          (G)         M
+ *   centroid      (G x 3)     sum w x / M
+ *   cov           (G x 6)     sum w (x - c)(x - c)^T / M in the order xx xy xz yy yz zz, the population form about the fp64
+ *                             centroid c, in a second pass over the points (a one-pass raw-moment form loses about |x|^2 / sigma^2
+ *                             of its digits far from the origin); 0 for a single member
+ *   aabb          (G x 6)     min x y z, max x y z: the exact minimum and maximum of the members' fp32 coordinates (the weight only
+ *                             decides membership), compared through the order-preserving integer map of the bits: -0 < +0
+ *   feature_mean  (G x C)     sum w f / M per channel, row i of the features at features + i * feature_stride; a non-finite
+ *                             feature element propagates into its channel of its group and is not filtered
+ * Every output is optional (NULL: not wanted, its work is skipped - without cov there is no second pass); at least one must be
+ * given.  An empty group: count 0, mass 0, zeros in centroid, cov and feature_mean, aabb = (+inf x 3, -inf x 3); P == 0 writes
+ * these for every group.  Every sum is accumulated in fp64 (a product of two fp32 values is exact there); every output is the fp64
+ * quotient rounded once to fp32.  The sums are gathered with atomics that arrive in a varying order: the float outputs are NOT
+ * bit-reproducible between two calls (as `acc` of the contribution pass); count and aabb are.  features: 16-byte row loads when
+ * C % 4 == 0, feature_stride % 4 == 0 and the pointer is 16-byte aligned, scalar loads otherwise - the same results.
+ * `scratch` = f3dgs_group_stats_scratch_bytes(G, C) bytes of device memory, 8-byte aligned, cleared by a launch of the call.
+ * F3DGS_ERR_INVALID_ARGUMENT before any device work: P < 0, G outside [1, F3DGS_GROUP_MAX_GROUPS], C outside [0,
+ * F3DGS_GROUP_MAX_CHANNELS], C > 0 without features, feature_mean with C == 0, feature_stride < C, a NULL groups or xyz while
+ * P > 0, every output NULL, a scratch that is NULL, misaligned or too small.  No host read, no allocation, no memset node:
+ * capturable as one linear graph (three to seven launches).
+ *
+ * f3dgs_group_merge: unites ADJACENT groups whose mean features agree.  Groups a != b are adjacent iff some slot s of some row i of
+ * the neighbour lists is an edge i -> j = idx[i, s] with 0 <= j < P, j != i, groups[i] = a and groups[j] = b both in [0, G), and -
+ * for a finite max_dist2 - dist2[i, s] <= max_dist2 (a NaN is no edge: f3dgs_knn_components' rules with "equal labels" turned into
+ * "different ids"); with mutual != 0 row j must hold i as well, each judged on its own slot.  Adjacent groups are united iff
+ * dot(m_a, m_b) / sqrt(dot(m_a, m_a) * dot(m_b, m_b)) >= min_cos, evaluated in fp64 on the fp32 rows m of feature_mean (G x C); a
+ * NaN or a zero norm is no merge.  group_root[g] (G) is the smallest id of g's merged set, for every g in [0, G) - a group nobody
+ * belongs to is its own root; groups_out[i] (P; may be `groups`) = group_root[groups[i]], -1 for an id outside [0, G).  status: one
+ * int32 on the device, always written: 0, non-zero only if a walk of the union-find reached its cap; never read here.  The result
+ * is integers and a function of the inputs alone unless an adjacent pair's cosine lies within rounding of min_cos.
+ * `scratch` = f3dgs_group_merge_scratch_bytes(G) bytes (the adjacency is G x G bits), 4-byte aligned, cleared by a launch.
+ * F3DGS_ERR_INVALID_ARGUMENT before any device work: P < 0, K outside [1, F3DGS_KNN_MAX_NEIGHBORS], G outside [1,
+ * F3DGS_GROUP_MERGE_MAX_GROUPS], C outside [1, F3DGS_GROUP_MAX_CHANNELS], a negative or NaN max_dist2, a NaN min_cos, a NULL
+ * feature_mean / group_root / status, a NULL groups / idx / groups_out while P > 0, a finite max_dist2 without dist2, a scratch
+ * that is NULL, misaligned or too small; P > 2^30: F3DGS_ERR_UNSUPPORTED.  Five launches, capturable.
+ */
+#define F3DGS_GROUP_MAX_GROUPS 65536
+#define F3DGS_GROUP_MAX_CHANNELS 4096
+#define F3DGS_GROUP_MERGE_MAX_GROUPS 4096 /* = F3DGS_INSTANCE_MAX_INSTANCES; the adjacency is G x G bits */
+size_t f3dgs_group_stats_scratch_bytes(int G, int C);
+int f3dgs_group_stats(int P, int G, int C, const int32_t* groups, const float* xyz, const float* weight /* or NULL */,
+                      const float* features /* NULL iff C == 0 */, int64_t feature_stride /* >= C, in elements */,
+                      int32_t* count, float* mass, float* centroid, float* cov, float* aabb, float* feature_mean /* each or NULL */,
+                      void* scratch, size_t scratch_bytes, void* stream /* hipStream_t */);
+size_t f3dgs_group_merge_scratch_bytes(int G);
+int f3dgs_group_merge(int P, int K, int G, int C, const int32_t* groups, const int32_t* idx, const float* dist2 /* or NULL */,
+                      float max_dist2, int mutual, const float* feature_mean /* G x C */, float min_cos, int32_t* group_root /* G */,
+                      int32_t* groups_out /* P, may alias groups */, int32_t* status /* device */, void* scratch,
+                      size_t scratch_bytes, void* stream /* hipStream_t */);
+
+/*
  * ---- Side channels of f3dgs_backward: threading contract -----------------------------------------------------------
  * The four setters below and f3dgs_set_feature_grad_lowres change how the f3dgs_backward calls OF THE CALLING HOST THREAD
  * behave.  All five are thread-local: they are invisible to, and unaffected by, any other thread.
