@@ -8,6 +8,8 @@
 //   component_filter(labels, root, size, min_size, largest, num_labels, labels_out): f3dgs_component_filter
 //   group_stats(groups, xyz, G, weight, features, want) -> (count, mass, centroid, cov, aabb, feature_mean), each or None: f3dgs_group_stats
 //   group_merge(groups, idx, dist2, max_dist2, mutual, feature_mean, min_cos, out) -> (groups_out, group_root, status): f3dgs_group_merge
+//   transform_gaussians(groups, quat, scale, translation, pivot, xyz, rotations, scales, linear, cov3d, sh_rest, rows, inplace)
+//       -> (xyz, rotations, scales, cov3d, sh_rest, status), each of the first five or None: f3dgs_transform_gaussians
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/extension.h>
@@ -238,6 +240,85 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> group_merge(const torch:
     return {groups_out, group_root, status};
 }
 
+// f3dgs_transform_gaussians.  The table: quat (G, 4), scale (G), translation (G, 3), pivot (G, 3) or None, contiguous float32.
+// Per-Gaussian tensors, each or None: xyz (P, 3), rotations (P, 4), scales (P, 3), cov3d (P, 6) contiguous float32; sh_rest
+// (P, n_rest, 3) float32, n_rest in {3, 8, 15}, contiguous in its last two dimensions with any row stride >= 3 n_rest (a view is
+// read in place).  rows: (M) int32 or None (the gather form).  inplace: the outputs ARE the inputs (not with rows).  Returns the
+// transformed tensors in the order of the arguments (None where none was given) and status (G) int32.  Nothing is read back.
+std::vector<c10::optional<torch::Tensor>> transform_gaussians(const torch::Tensor& groups, const torch::Tensor& quat, const torch::Tensor& scale,
+                                                              const torch::Tensor& translation, const c10::optional<torch::Tensor>& pivot,
+                                                              const c10::optional<torch::Tensor>& xyz,
+                                                              const c10::optional<torch::Tensor>& rotations,
+                                                              const c10::optional<torch::Tensor>& scales, bool linear,
+                                                              const c10::optional<torch::Tensor>& cov3d,
+                                                              const c10::optional<torch::Tensor>& sh_rest,
+                                                              const c10::optional<torch::Tensor>& rows, bool inplace) {
+    TORCH_CHECK(groups.is_cuda(), "groups must live on a HIP device: the object transforms have no CPU path");
+    TORCH_CHECK(groups.dim() == 1 && groups.scalar_type() == torch::kInt32 && groups.is_contiguous(), "groups: contiguous int32 (P) expected");
+    const long long P = groups.size(0);
+    TORCH_CHECK(P <= (1ll << 30), "too many points");
+    const auto dev = groups.device();
+    auto is_table = [&](const torch::Tensor& t, long long G, long long w) {
+        return t.scalar_type() == torch::kFloat32 && t.device() == dev && t.is_contiguous() &&
+               (w == 0 ? (t.dim() == 1 && t.size(0) == G) : (t.dim() == 2 && t.size(0) == G && t.size(1) == w));
+    };
+    TORCH_CHECK(scale.dim() == 1, "scale: contiguous float32 (G) on the groups' device expected");
+    const long long G = scale.size(0);
+    TORCH_CHECK(G >= 1 && G <= F3DGS_GROUP_MAX_GROUPS, "G = ", G, ": 1 .. ", F3DGS_GROUP_MAX_GROUPS, " groups are taken");
+    TORCH_CHECK(is_table(scale, G, 0), "scale: contiguous float32 (G) on the groups' device expected");
+    TORCH_CHECK(is_table(quat, G, 4), "quat: contiguous float32 (G, 4) on the groups' device expected");
+    TORCH_CHECK(is_table(translation, G, 3), "translation: contiguous float32 (G, 3) on the groups' device expected");
+    if (pivot) TORCH_CHECK(is_table(*pivot, G, 3), "pivot: contiguous float32 (G, 3) on the groups' device expected");
+    const c10::optional<torch::Tensor>* in[4] = {&xyz, &rotations, &scales, &cov3d};
+    const char* names[4] = {"xyz", "rotations", "scales", "cov3d"};
+    const long long width[4] = {3, 4, 3, 6};
+    for (int a = 0; a < 4; a++)
+        if (*in[a]) TORCH_CHECK(is_table(**in[a], P, width[a]), names[a], ": contiguous float32 (P, ", width[a], ") on the groups' device expected");
+    int n_rest = 0;
+    long long stride = 0;
+    if (sh_rest) {
+        TORCH_CHECK(sh_rest->dim() == 3 && sh_rest->size(0) == P && sh_rest->size(2) == 3 && sh_rest->scalar_type() == torch::kFloat32 &&
+                        sh_rest->device() == dev, "sh_rest: float32 (P, n_rest, 3) on the groups' device expected");
+        TORCH_CHECK(sh_rest->size(1) == 3 || sh_rest->size(1) == 8 || sh_rest->size(1) == 15, "sh_rest: n_rest = ", sh_rest->size(1),
+                    ", 3, 8 and 15 are taken");
+        n_rest = (int)sh_rest->size(1);
+        stride = P > 1 ? sh_rest->stride(0) : 3 * n_rest;
+        TORCH_CHECK(P == 0 || (sh_rest->stride(2) == 1 && sh_rest->stride(1) == 3 && stride >= 3 * n_rest),
+                    "sh_rest: rows of n_rest x 3 contiguous floats and a row stride >= 3 n_rest expected");
+    }
+    TORCH_CHECK(xyz || rotations || scales || cov3d || sh_rest, "no per-Gaussian tensor given");
+    TORCH_CHECK(!(rows && inplace), "inplace and rows exclude each other");
+    long long M = P;
+    if (rows) {
+        TORCH_CHECK(rows->dim() == 1 && rows->scalar_type() == torch::kInt32 && rows->device() == dev && rows->is_contiguous(),
+                    "rows: contiguous int32 (M) on the groups' device expected");
+        M = rows->size(0);
+        TORCH_CHECK(M < (1ll << 31), "too many rows");
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto floats = quat.options();
+    std::vector<c10::optional<torch::Tensor>> out(6);
+    for (int a = 0; a < 4; a++)
+        if (*in[a]) out[a] = inplace ? **in[a] : torch::empty({M, width[a]}, floats);
+    if (sh_rest) out[4] = inplace ? *sh_rest : torch::empty({M, (long long)n_rest, 3}, floats);
+    torch::Tensor status = torch::empty({G}, groups.options());
+    out[5] = status;
+    const size_t bytes = f3dgs_transform_gaussians_scratch_bytes((int)G);
+    torch::Tensor scratch = torch::empty({(long long)bytes}, floats.dtype(torch::kByte));
+    // (an empty tensor has no address: with P == 0 or M == 0 nothing is read or written through these)
+    float* const nowhere = static_cast<float*>(scratch.data_ptr());
+    auto ip = [&](const c10::optional<torch::Tensor>& t) -> const float* { return !t ? nullptr : (P > 0 ? t->data_ptr<float>() : nowhere); };
+    auto op = [&](int a) -> float* { return !out[a] ? nullptr : (M > 0 && P > 0 ? out[a]->data_ptr<float>() : nowhere + 64); };
+    const int rc = f3dgs_transform_gaussians(
+        (int)P, (int)G, quat.data_ptr<float>(), scale.data_ptr<float>(), translation.data_ptr<float>(), pivot ? pivot->data_ptr<float>() : nullptr,
+        P > 0 ? groups.data_ptr<int32_t>() : nullptr, rows ? (M > 0 ? rows->data_ptr<int32_t>() : reinterpret_cast<const int32_t*>(nowhere)) : nullptr,
+        (int)M, ip(xyz), ip(rotations), ip(scales), linear ? F3DGS_TRANSFORM_SCALES_LINEAR : F3DGS_TRANSFORM_SCALES_LOG, ip(cov3d), ip(sh_rest),
+        n_rest, stride, op(0), op(1), op(2), op(3), op(4), inplace ? stride : 3 * n_rest, status.data_ptr<int32_t>(), scratch.data_ptr(), bytes,
+        current_stream(groups));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("transform_gaussians: ") + f3dgs_last_error());
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -248,6 +329,7 @@ PYBIND11_MODULE(_C, m) {
     m.def("component_filter", &component_filter);
     m.def("group_stats", &group_stats);
     m.def("group_merge", &group_merge);
+    m.def("transform_gaussians", &transform_gaussians);
     m.attr("GROUP_COUNT") = (int)GROUP_COUNT;
     m.attr("GROUP_MASS") = (int)GROUP_MASS;
     m.attr("GROUP_CENTROID") = (int)GROUP_CENTROID;

@@ -1022,6 +1022,74 @@ int f3dgs_group_merge(int P, int K, int G, int C, const int32_t* groups, const i
                       size_t scratch_bytes, void* stream /* hipStream_t */);
 
 /*
+ * Object transforms (ABI 3.21; no counterpart in the reference, whose editing stops at delete / extract / recolour): the
+ * Gaussians of every group moved, turned and scaled by the group's own similarity transform, every group in the same launch.
+ *
+ * The table, G rows (1 <= G <= F3DGS_GROUP_MAX_GROUPS) in device memory: quat (G x 4) in the model's order (w, x, y, z), scale
+ * (G), translation (G x 3), pivot (G x 3, or NULL: the origin).  The quaternion is normalised in fp64 on the device, R =
+ * R(q / |q|) by the rasterizer's formula (preprocess.hip; oracle/torch_oracle.py: _quat_to_rot), and the map of group g is
+ *     x' = s R (x - p) + p + t.
+ * A row is INVALID iff one of its entries is not finite, |q| is 0 (or not finite), or s <= 0.  status[g] (G, int32, always
+ * written): 0 for a valid row, otherwise the first of F3DGS_TRANSFORM_BAD_QUAT (an entry of quat is not finite), _ZERO_QUAT,
+ * _BAD_SCALE (not finite), _NONPOSITIVE_SCALE, _BAD_TRANSLATION, _BAD_PIVOT that applies.  The members of an invalid group are
+ * treated exactly as non-members.  Gaussian i is TRANSFORMED iff 0 <= groups[i] < G and that row is valid; any integers may stand
+ * in `groups` (P, int32).
+ *
+ * Per-Gaussian inputs, each optional (NULL), at least one; each given input needs its output and the other way round:
+ *   xyz        (P x 3)   x' as above
+ *   rotations  (P x 4)   the Hamilton product q_T (x) q, q_T the normalised quaternion of the table.  This is exact for the model,
+ *                        whose get_rotation normalises.  The rasterizer does NOT normalise (forward.cu:128): fed |q| != 1 it
+ *                        builds |q|^2 R + (1 - |q|^2) I, before the transform and after it alike, and that matrix does not turn
+ *                        with R.  A caller who hands un-normalised quaternions straight to the rasterizer must normalise first.
+ *   scales     (P x 3)   scale_mode F3DGS_TRANSFORM_SCALES_LOG: the model's raw _scaling, + ln s; _LINEAR: activated scales, * s
+ *   cov3d      (P x 6)   xx xy xz yy yz zz as cov3D_precomp: s^2 R Sigma R^T
+ *   sh_rest    n_rest in {0, 3, 8, 15} coefficients of 3 colours per Gaussian (degree 0 .. 3 without the DC term), row i at
+ *              sh_rest + i * sh_stride floats, coefficient k colour c at 3 k + c: the model's _features_rest (P, 15, 3) with
+ *              sh_stride = 45, or shs + 3 of a (P, 16, 3) tensor with sh_stride = 48, read (and written) in place.  The
+ *              coefficients of band l become D_l(R) c, D_l the (2l + 1)^2 matrix with sum_m c'_m Y_m(R d) = sum_m c_m Y_m(d) for
+ *              every unit d in the rasterizer's basis (the constants C1, C2[], C3[] with their signs): a turned object keeps
+ *              its view-dependent colour on its own surface.  sh_rest == NULL iff n_rest == 0.
+ * DC colour, opacity and semantic features are invariant and are not taken.  A non-finite value of a Gaussian propagates
+ * (through the whole band, for a coefficient); there is no per-Gaussian special case.
+ *
+ * Two forms.  src_rows == NULL: every output has P rows (M is ignored) and may be its input - the same pointer and, for sh_rest,
+ * the same stride.  A row that is not transformed is copied unchanged, and where output and input are the same array it is not
+ * written at all.  src_rows (M, int32): the GATHER form - output row j is the transform of input row src_rows[j] under that row's
+ * group (a copy where it is not transformed), a row of zeros for an index outside [0, P): "a second instance 17 over there" is
+ * one call into appended rows.  An output that overlaps an input in any other way is refused.  With P == 0, or M == 0 in the
+ * gather form, only status is written.
+ *
+ * Numerics: one small kernel per call builds, per group and in fp64, s R, p, p + t, q / |q|, ln s, s and D_1, D_2, D_3 (83
+ * entries; the recursion of Ivanic and Ruedenberg in the entries of R); the per-Gaussian kernel accumulates every output element
+ * as one fp64 chain of fused multiply-adds and rounds once to fp32.  An output that sums n terms t_k lies within
+ * ulp32(v) / 2 + 4 n 2^-53 sum|t_k| of its fp64 value v (n = 5 for xyz: the three products, p and t; 4 for rotations, 2 / 1 for
+ * scales, 9 for cov3d, 2l + 1 for band l) - wherever the scene lies.  No bit promise beyond "rows that are not transformed are
+ * untouched" and "the same inputs give the same outputs" (no atomics).
+ * `scratch` = f3dgs_transform_gaussians_scratch_bytes(G) bytes of device memory, 8-byte aligned (the table).
+ * F3DGS_ERR_INVALID_ARGUMENT before any device work: P < 0, G outside [1, F3DGS_GROUP_MAX_GROUPS], a NULL quat / scale /
+ * translation / status, M < 0 with src_rows, n_rest outside {0, 3, 8, 15} or at odds with sh_rest, an unknown scale_mode, every
+ * input NULL, an input without its output or an output without its input, a stride below 3 n_rest, a NULL groups while P > 0,
+ * an output that overlaps an input other than in place, a scratch that is NULL, misaligned or too small; P > 2^30:
+ * F3DGS_ERR_UNSUPPORTED.  No host read, no allocation, no memset node, no option: two launches, capturable.
+ */
+#define F3DGS_TRANSFORM_SCALES_LOG 0
+#define F3DGS_TRANSFORM_SCALES_LINEAR 1
+#define F3DGS_TRANSFORM_BAD_QUAT 1
+#define F3DGS_TRANSFORM_ZERO_QUAT 2
+#define F3DGS_TRANSFORM_BAD_SCALE 3
+#define F3DGS_TRANSFORM_NONPOSITIVE_SCALE 4
+#define F3DGS_TRANSFORM_BAD_TRANSLATION 5
+#define F3DGS_TRANSFORM_BAD_PIVOT 6
+size_t f3dgs_transform_gaussians_scratch_bytes(int G);
+int f3dgs_transform_gaussians(int P, int G, const float* quat, const float* scale, const float* translation,
+                              const float* pivot /* or NULL */, const int32_t* groups, const int32_t* src_rows /* or NULL */, int M,
+                              const float* xyz, const float* rotations, const float* scales /* each or NULL */, int scale_mode,
+                              const float* cov3d /* or NULL */, const float* sh_rest /* NULL iff n_rest == 0 */, int n_rest,
+                              int64_t sh_stride /* in floats */, float* xyz_out, float* rotations_out, float* scales_out,
+                              float* cov3d_out, float* sh_rest_out, int64_t sh_out_stride, int32_t* status /* G */, void* scratch,
+                              size_t scratch_bytes, void* stream /* hipStream_t */);
+
+/*
  * ---- Side channels of f3dgs_backward: threading contract -----------------------------------------------------------
  * The four setters below and f3dgs_set_feature_grad_lowres change how the f3dgs_backward calls OF THE CALLING HOST THREAD
  * behave.  All five are thread-local: they are invisible to, and unaffected by, any other thread.
