@@ -10,6 +10,9 @@
 //   group_merge(groups, idx, dist2, max_dist2, mutual, feature_mean, min_cos, out) -> (groups_out, group_root, status): f3dgs_group_merge
 //   transform_gaussians(groups, quat, scale, translation, pivot, xyz, rotations, scales, linear, cov3d, sh_rest, rows, inplace)
 //       -> (xyz, rotations, scales, cov3d, sh_rest, status), each of the first five or None: f3dgs_transform_gaussians
+//   codebook_assign(features, centroids, flags, prev_codes, weight, codes_out, want_dist2, inertia_out, moved_out) -> (codes, dist2 or None):
+//       f3dgs_codebook_assign; codebook_update(features, codes, weight, centroids, flags, iteration, count_out): f3dgs_codebook_update, in place;
+//       codebook_workspace_bytes(K, C)
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/extension.h>
@@ -319,6 +322,90 @@ std::vector<c10::optional<torch::Tensor>> transform_gaussians(const torch::Tenso
     return out;
 }
 
+// the (P, C) features of the codebook entries: float32, unit stride along C, any row stride >= C (a view is read in place)
+long long codebook_features(const torch::Tensor& features, long long* P, int* C) {
+    TORCH_CHECK(features.is_cuda(), "features must live on a HIP device: the codebooks have no CPU path");
+    TORCH_CHECK(features.dim() == 2 && features.scalar_type() == torch::kFloat32, "features: float32 (P, C) expected");
+    TORCH_CHECK(features.size(1) >= 1 && features.size(1) <= F3DGS_CODEBOOK_MAX_CHANNELS, "C = ", features.size(1), ": 1 .. ",
+                F3DGS_CODEBOOK_MAX_CHANNELS, " channels are taken");
+    *P = features.size(0);
+    *C = (int)features.size(1);
+    TORCH_CHECK(*P < (1ll << 31) - 129, "too many rows");
+    const long long stride = *P > 1 ? features.stride(0) : *C;
+    TORCH_CHECK(*P == 0 || ((*C == 1 || features.stride(1) == 1) && stride >= *C), "features: unit stride along C and a row stride >= C expected");
+    return stride;
+}
+
+void codebook_centroids(const torch::Tensor& centroids, const torch::Tensor& features, int C) {
+    TORCH_CHECK(centroids.dim() == 2 && centroids.size(1) == C && centroids.scalar_type() == torch::kFloat32 &&
+                    centroids.device() == features.device() && centroids.is_contiguous(),
+                "centroids: contiguous float32 (K, C) on the features' device expected");
+    TORCH_CHECK(centroids.size(0) >= 1 && centroids.size(0) <= F3DGS_CODEBOOK_MAX_CENTROIDS, "K = ", centroids.size(0), ": 1 .. ",
+                F3DGS_CODEBOOK_MAX_CENTROIDS, " centroids are taken");
+}
+
+void codebook_rows(const c10::optional<torch::Tensor>& t, const torch::Tensor& features, long long n, c10::ScalarType type, const char* what) {
+    if (!t) return;
+    TORCH_CHECK(t->dim() == 1 && t->size(0) == n && t->scalar_type() == type && t->device() == features.device() && t->is_contiguous(), what);
+}
+
+// f3dgs_codebook_assign.  codes_out: the caller's (P) int32 (it may be prev_codes) or None; inertia_out: one float64, moved_out: one
+// int32 on the device, each or None - a slot of a per-iteration tensor.  Nothing is read back.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> codebook_assign(
+    const torch::Tensor& features, const torch::Tensor& centroids, int flags, const c10::optional<torch::Tensor>& prev_codes,
+    const c10::optional<torch::Tensor>& weight, const c10::optional<torch::Tensor>& codes_out, bool want_dist2,
+    const c10::optional<torch::Tensor>& inertia_out, const c10::optional<torch::Tensor>& moved_out) {
+    long long P;
+    int C;
+    const long long stride = codebook_features(features, &P, &C);
+    codebook_centroids(centroids, features, C);
+    const int K = (int)centroids.size(0);
+    codebook_rows(prev_codes, features, P, torch::kInt32, "prev_codes: contiguous int32 (P) on the features' device expected");
+    codebook_rows(codes_out, features, P, torch::kInt32, "codes_out: contiguous int32 (P) on the features' device expected");
+    codebook_rows(weight, features, P, torch::kFloat32, "weight: contiguous float32 (P) on the features' device expected");
+    codebook_rows(inertia_out, features, 1, torch::kFloat64, "inertia_out: one float64 on the features' device expected");
+    codebook_rows(moved_out, features, 1, torch::kInt32, "moved_out: one int32 on the features' device expected");
+    TORCH_CHECK(!moved_out || prev_codes, "moved_out needs prev_codes");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(features.device());
+    torch::Tensor codes = codes_out ? *codes_out : torch::empty({P}, features.options().dtype(torch::kInt32));
+    c10::optional<torch::Tensor> dist2;
+    if (want_dist2) dist2 = torch::empty({P}, features.options());
+    const size_t bytes = f3dgs_codebook_workspace_bytes(K, C);
+    torch::Tensor workspace = torch::empty({(long long)bytes}, features.options().dtype(torch::kByte));
+    // (an empty tensor has no address: with P == 0 nothing is read through these)
+    const float* feat = P > 0 ? features.data_ptr<float>() : static_cast<const float*>(workspace.data_ptr());
+    const int rc = f3dgs_codebook_assign((int)P, K, C, feat, stride, centroids.data_ptr<float>(), flags,
+                                         (prev_codes && P > 0) ? prev_codes->data_ptr<int32_t>() : nullptr,
+                                         (weight && P > 0) ? weight->data_ptr<float>() : nullptr,
+                                         P > 0 ? codes.data_ptr<int32_t>() : nullptr, (dist2 && P > 0) ? dist2->data_ptr<float>() : nullptr,
+                                         inertia_out ? inertia_out->data_ptr<double>() : nullptr,
+                                         (moved_out && (P > 0 || prev_codes)) ? moved_out->data_ptr<int32_t>() : nullptr, workspace.data_ptr(), bytes,
+                                         current_stream(features));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("codebook_assign: ") + f3dgs_last_error());
+    return {codes, dist2};
+}
+
+// f3dgs_codebook_update: `centroids` (K, C) is moved in place; count_out: the caller's (K) int32 or None
+void codebook_update(const torch::Tensor& features, const torch::Tensor& codes, const c10::optional<torch::Tensor>& weight,
+                     torch::Tensor centroids, int flags, int iteration, const c10::optional<torch::Tensor>& count_out) {
+    long long P;
+    int C;
+    const long long stride = codebook_features(features, &P, &C);
+    codebook_centroids(centroids, features, C);
+    const int K = (int)centroids.size(0);
+    codebook_rows(codes, features, P, torch::kInt32, "codes: contiguous int32 (P) on the features' device expected");
+    codebook_rows(weight, features, P, torch::kFloat32, "weight: contiguous float32 (P) on the features' device expected");
+    codebook_rows(count_out, features, K, torch::kInt32, "count_out: contiguous int32 (K) on the features' device expected");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(features.device());
+    const size_t bytes = f3dgs_codebook_update_scratch_bytes(K, C);
+    torch::Tensor scratch = torch::empty({(long long)bytes}, features.options().dtype(torch::kByte));
+    const float* feat = P > 0 ? features.data_ptr<float>() : static_cast<const float*>(scratch.data_ptr());
+    const int rc = f3dgs_codebook_update((int)P, K, C, feat, stride, P > 0 ? codes.data_ptr<int32_t>() : nullptr,
+                                         (weight && P > 0) ? weight->data_ptr<float>() : nullptr, flags, iteration, centroids.data_ptr<float>(),
+                                         count_out ? count_out->data_ptr<int32_t>() : nullptr, scratch.data_ptr(), bytes, current_stream(features));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("codebook_update: ") + f3dgs_last_error());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -330,6 +417,13 @@ PYBIND11_MODULE(_C, m) {
     m.def("group_stats", &group_stats);
     m.def("group_merge", &group_merge);
     m.def("transform_gaussians", &transform_gaussians);
+    m.def("codebook_assign", &codebook_assign);
+    m.def("codebook_update", &codebook_update);
+    m.def("codebook_workspace_bytes", [](int K, int C) { return (long long)f3dgs_codebook_workspace_bytes(K, C); });
+    m.attr("CODEBOOK_COSINE") = F3DGS_CODEBOOK_COSINE;
+    m.attr("CODEBOOK_RESEED_EMPTY") = F3DGS_CODEBOOK_RESEED_EMPTY;
+    m.attr("CODEBOOK_MAX_CENTROIDS") = F3DGS_CODEBOOK_MAX_CENTROIDS;
+    m.attr("CODEBOOK_MAX_CHANNELS") = F3DGS_CODEBOOK_MAX_CHANNELS;
     m.attr("GROUP_COUNT") = (int)GROUP_COUNT;
     m.attr("GROUP_MASS") = (int)GROUP_MASS;
     m.attr("GROUP_CENTROID") = (int)GROUP_CENTROID;

@@ -30,6 +30,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "group_sums.h"
 #include "union_find.h"
 
 namespace f3dgs {
@@ -310,7 +311,7 @@ __global__ void __launch_bounds__(256) group_pass_kernel(Job job) {
         uint32_t key = NO_KEY;
         if (i < (size_t)job.P) {
             const int g = job.groups[i];
-            const float x = job.xyz[i * 3], y = job.xyz[i * 3 + 1], z = job.xyz[i * 3 + 2];
+            const float x = job.xyz ? job.xyz[i * 3] : 0.f, y = job.xyz ? job.xyz[i * 3 + 1] : 0.f, z = job.xyz ? job.xyz[i * 3 + 2] : 0.f;   // (no xyz: group_sums.h)
             const float w = job.weight ? job.weight[i] : 1.f;
             if (is_member(g, job.G, x, y, z, w)) {
                 key = ((uint32_t)g << LOG_ROWS) | (uint32_t)li;
@@ -370,6 +371,25 @@ __global__ void __launch_bounds__(256) group_finish_features_kernel(size_t n, in
 }
 
 unsigned blocks_of(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+int feature_lanes(int C) {
+    const int need = (C + 3) / 4;
+    int lanes = MOMENT_LANES;                        // (not fewer: every sub-group of a chunk flushes at least once per channel)
+    while (lanes < need && lanes < 64) lanes <<= 1;
+    return lanes;
+}
+
+bool vector_rows(const float* features, int C, int64_t stride) { return C % 4 == 0 && stride % 4 == 0 && aligned16(features); }
+
+void launch_clear_and_pass0(const Job& job, bool vec, hipStream_t st) {
+    const size_t doubles = table_doubles(job.G, job.C);
+    hipLaunchKernelGGL(group_clear_kernel, dim3(std::min(blocks_of(doubles, 256), 4096u)), dim3(256), 0, st, job.G, doubles, job.t);
+    if (job.P > 0) {
+        const unsigned chunks = blocks_of((size_t)job.P, ROWS);
+        if (vec) hipLaunchKernelGGL((group_pass_kernel<0, true>), dim3(chunks), dim3(256), 0, st, job);
+        else hipLaunchKernelGGL((group_pass_kernel<0, false>), dim3(chunks), dim3(256), 0, st, job);
+    }
+}
 
 // ---- the merge ---------------------------------------------------------------------------------------------------------------
 
@@ -475,6 +495,21 @@ __global__ void __launch_bounds__(256) merge_gather_kernel(int P, int G, const i
 
 }  // namespace
 
+// group_sums.h
+size_t group_feature_sums_bytes(int G, int C) { return table_bytes(G, C) + 8; }
+
+GroupSums launch_group_feature_sums(int P, int G, int C, const int32_t* groups, const float* weight, const float* features, int64_t stride,
+                                    void* scratch, hipStream_t st) {
+    Job job{};
+    job.P = P, job.G = G, job.C = C;
+    job.groups = groups, job.xyz = nullptr, job.weight = weight, job.features = features, job.stride = stride;
+    job.t = carve_table(scratch, G, C);
+    job.roles = ROLE_MASS | ROLE_COUNT;
+    job.lanes_per_row = feature_lanes(C);
+    launch_clear_and_pass0(job, vector_rows(features, C, stride), st);
+    return GroupSums{job.t.mass, job.t.feat, job.t.count};
+}
+
 }  // namespace f3dgs
 
 using namespace f3dgs;
@@ -513,18 +548,10 @@ int f3dgs_group_stats(int P, int G, int C, const int32_t* groups, const float* x
     job.t = carve_table(scratch, G, C);
     job.roles = ((mass || centroid || cov || feature_mean) ? ROLE_MASS : 0u) | ((centroid || cov) ? ROLE_SUM : 0u) | (aabb ? ROLE_BOX : 0u) |
                 (count ? ROLE_COUNT : 0u);
-    const bool vec = C % 4 == 0 && feature_stride % 4 == 0 && aligned16(features);
-    if (feature_mean) {
-        const int need = (C + 3) / 4;
-        job.lanes_per_row = MOMENT_LANES;            // (not fewer: every sub-group of a chunk flushes at least once per channel)
-        while (job.lanes_per_row < need && job.lanes_per_row < 64) job.lanes_per_row <<= 1;
-    }
-    const size_t doubles = table_doubles(G, C);
+    if (feature_mean) job.lanes_per_row = feature_lanes(C);
     const unsigned groups_blocks = blocks_of((size_t)G, 256), chunks = blocks_of((size_t)P, ROWS);
-    hipLaunchKernelGGL(group_clear_kernel, dim3(std::min(blocks_of(doubles, 256), 4096u)), dim3(256), 0, st, G, doubles, job.t);
+    launch_clear_and_pass0(job, vector_rows(features, C, feature_stride), st);
     if (P > 0) {
-        if (vec) hipLaunchKernelGGL((group_pass_kernel<0, true>), dim3(chunks), dim3(256), 0, st, job);
-        else hipLaunchKernelGGL((group_pass_kernel<0, false>), dim3(chunks), dim3(256), 0, st, job);
         if (cov) {
             hipLaunchKernelGGL(group_center_kernel, dim3(groups_blocks), dim3(256), 0, st, G, job.t);
             hipLaunchKernelGGL((group_pass_kernel<1, false>), dim3(chunks), dim3(256), 0, st, job);

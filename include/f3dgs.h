@@ -1090,6 +1090,60 @@ int f3dgs_transform_gaussians(int P, int G, const float* quat, const float* scal
                               size_t scratch_bytes, void* stream /* hipStream_t */);
 
 /*
+ * Feature codebooks (ABI 3.22; no counterpart in the reference, which stores and writes every semantic feature in full): the two
+ * halves of Lloyd's iteration over the per-Gaussian features - vector or product quantisation of the features, and clustering of
+ * the Gaussians where no label map and no masks exist.  `features`: P rows of C float32, row i at features + i * feature_stride
+ * (feature_stride >= C, in elements; the channel stride is 1): the model's (P, 1, C) tensor, a column slice and a row-strided view
+ * are read in place.  `centroids`: (K x C) float32, contiguous.  1 <= K <= F3DGS_CODEBOOK_MAX_CENTROIDS, 1 <= C <=
+ * F3DGS_CODEBOOK_MAX_CHANNELS, P >= 0.
+ *
+ * f3dgs_codebook_assign: codes[i] (P, int32) = the index of the centroid nearest to row i.
+ *   L2 (flags == 0)         minimises  score_ik = |c_k|^2 - 2 x_i . c_k
+ *   F3DGS_CODEBOOK_COSINE   maximises  x_i . c^_k, c^_k = c_k / |c_k| (a zero centroid: c^_k = 0, it scores 0); score_ik = -x_i . c^_k
+ * |c_k|^2 and c^_k are computed per row in fp64 and rounded once to fp32 by a first launch, into `workspace`.  The dot product is
+ * ONE fp32 fmaf chain over the channels ascending from 0 (v_mfma_f32_32x32x2_f32: bit for bit such a chain; channels past C are
+ * zeros), score = fmaf(-2, dot, |c_k|^2) or -dot: a code is a function of the inputs alone, not of the grid or of P.  The lowest
+ * score wins, the lowest k among equal scores.  A score that is not finite never wins: a centroid with a non-finite element, or one
+ * whose |c_k|^2 or dot product overflows fp32.  A row with a non-finite element gets code -1, as does every row if no score is
+ * finite.  The (P, K) scores are never stored.
+ * Optional outputs (NULL: not wanted), all in device memory, none read back:
+ *   dist2    (P) float32   sum_c (x_ic - c_kc)^2 of the winner k, or 1 - cos(x_i, c_k) under the cosine metric (cos = 0 where x_i or
+ *                          c_k is zero), recomputed for the winner alone in fp64 from the caller's centroids and rounded once; 0
+ *                          for code -1
+ *   inertia  one double    sum of w_i * dist2_i (the rounded fp32 value) over the rows with a code >= 0 and 0 < w_i < inf (w_i =
+ *                          weight[i], 1 for a NULL weight), added in fp64 (a partial sum per 256 rows, then atomics: the last bits
+ *                          vary between calls).  The weight excludes a row from this sum and from the update, never from codes.
+ *   moved    one int32     the number of rows with codes[i] != prev_codes[i] (needs prev_codes; codes may BE prev_codes)
+ * `workspace` = f3dgs_codebook_workspace_bytes(K, C) bytes of device memory, 16-byte aligned: it depends on K and C only.
+ * F3DGS_ERR_INVALID_ARGUMENT before any device work: P < 0, K or C outside their limits, unknown flags, feature_stride < C, a NULL
+ * centroids, a NULL features or codes while P > 0, moved without prev_codes, a misaligned inertia, a workspace that is NULL,
+ * misaligned or too small; P > 2^31 - 129: F3DGS_ERR_UNSUPPORTED.  One to three launches, no host read, no allocation: capturable.
+ *
+ * f3dgs_codebook_update: centroids[k] (in place) = sum w_i x_i / sum w_i over the rows with codes[i] == k and 0 < w_i < inf, every
+ * sum in fp64 (f3dgs_group_stats' accumulation with the codes as ids: the sums meet in a varying order) and the quotient rounded
+ * once; with F3DGS_CODEBOOK_COSINE the fp64 mean is divided by its fp64 length before the rounding (a zero mean stays zero).
+ * count[k] (K, int32, or NULL) = the number of those rows.  A code outside [0, K) belongs to no centroid.  A centroid without
+ * members keeps its row; with F3DGS_CODEBOOK_RESEED_EMPTY it takes the features of row (k * 2654435761 + iteration * 40503) mod P
+ * (in uint64) instead - unless P == 0 or that row holds a non-finite element, then it keeps its row.  A non-finite feature of a
+ * member propagates into its channel.  `scratch` = f3dgs_codebook_update_scratch_bytes(K, C) bytes, 8-byte aligned, cleared by a
+ * launch of the call.  F3DGS_ERR_INVALID_ARGUMENT before any device work: as above, a negative iteration.  Two or three launches,
+ * capturable.
+ */
+#define F3DGS_CODEBOOK_COSINE 1
+#define F3DGS_CODEBOOK_RESEED_EMPTY 2
+#define F3DGS_CODEBOOK_MAX_CENTROIDS 65536 /* = F3DGS_GROUP_MAX_GROUPS */
+#define F3DGS_CODEBOOK_MAX_CHANNELS 4096   /* = F3DGS_GROUP_MAX_CHANNELS */
+size_t f3dgs_codebook_workspace_bytes(int K, int C);
+int f3dgs_codebook_assign(int P, int K, int C, const float* features, int64_t feature_stride /* >= C, in elements */,
+                          const float* centroids /* K x C */, int flags, const int32_t* prev_codes /* or NULL */,
+                          const float* weight /* or NULL */, int32_t* codes /* P, may alias prev_codes */, float* dist2, double* inertia,
+                          int32_t* moved /* each or NULL */, void* workspace, size_t workspace_bytes, void* stream /* hipStream_t */);
+size_t f3dgs_codebook_update_scratch_bytes(int K, int C);
+int f3dgs_codebook_update(int P, int K, int C, const float* features, int64_t feature_stride, const int32_t* codes,
+                          const float* weight /* or NULL */, int flags, int iteration, float* centroids /* K x C, in place */,
+                          int32_t* count /* K, or NULL */, void* scratch, size_t scratch_bytes, void* stream /* hipStream_t */);
+
+/*
  * ---- Side channels of f3dgs_backward: threading contract -----------------------------------------------------------
  * The four setters below and f3dgs_set_feature_grad_lowres change how the f3dgs_backward calls OF THE CALLING HOST THREAD
  * behave.  All five are thread-local: they are invisible to, and unaffected by, any other thread.
