@@ -28,6 +28,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "decoder_tile.h"      // f32x16, mfma_row (the tiling here is its own)
 #include "group_sums.h"
 
 namespace f3dgs {
@@ -41,19 +42,10 @@ constexpr int LS = CH + 4;         // words of a row of the LDS image (16-byte r
 static_assert(F3DGS_CODEBOOK_MAX_CENTROIDS == F3DGS_GROUP_MAX_GROUPS && F3DGS_CODEBOOK_MAX_CHANNELS == F3DGS_GROUP_MAX_CHANNELS,
               "the update runs the codes through the group sums");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int mfma_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 D layout
 __device__ __forceinline__ bool finite32(float v) { return fabsf(v) < INFINITY; }                  // (false for NaN)
 
 size_t offsets_bytes(int K) { return (((size_t)K * sizeof(float)) + 15) & ~(size_t)15; }
 size_t workspace_bytes(int K, int C) { return offsets_bytes(K) + (size_t)K * C * sizeof(float) + 16; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 // one wave per centroid
 __global__ void __launch_bounds__(256) codebook_prepare_kernel(int K, int C, const float* __restrict__ centroids, int cosine,

@@ -454,6 +454,31 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+// exclusive prefix of v over the 256 threads of a workgroup, and the sum; s_w: four values in LDS
+template <typename T>
+__device__ __forceinline__ T block_scan(T v, T* s_w, T& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T inc = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    __syncthreads();
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    T before = 0;
+    total = 0;
+    for (int w = 0; w < 4; w++) {
+        if (w < wave) before += s_w[w];
+        total += s_w[w];
+    }
+    return before + inc - v;
+}
 // XCD-aware bijective remap of a linear workgroup id: workgroup b runs on XCD b % 8 (observed,
 // MI355X_MICROARCH.md), so give every XCD one contiguous run of tiles to keep neighbouring tiles
 // (which share splat records and feature vectors) behind the same L2.

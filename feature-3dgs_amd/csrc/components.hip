@@ -135,26 +135,6 @@ __global__ void __launch_bounds__(256) comp_spread_kernel(int P, const int32_t* 
     if (r >= 0 && r < i) size[i] = size[r];                                  // (a root keeps its count; nobody writes a root's)
 }
 
-// exclusive prefix of v over the 256 threads, and the sum
-__device__ __forceinline__ int block_scan(int v, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-    for (int w = 0; w < 4; w++) {
-        if (w < wave) before += s_w[w];
-        total += s_w[w];
-    }
-    return before + inc - v;
-}
-
 __global__ void __launch_bounds__(256) comp_count_kernel(int P, const int32_t* __restrict__ root, int32_t* __restrict__ sums) {
     __shared__ int s_w[4];
     int n = 0;

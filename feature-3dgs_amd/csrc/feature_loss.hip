@@ -15,19 +15,18 @@
 //                  from an LDS copy of g_y; only the SIGNS of r leave the kernel (1 byte per element)
 //   K3 dW, db      dW = g_y^T X, db = sum g_y: split over pixel ranges, A operand expanded from the sign bytes
 //   K4 resize^T    dL/dfeature_map (C,H,W) gathered from g_x (no atomics: every source pixel sums its own few outputs)
-// The decoder is the one dense contraction next to the rasterizer (v_mfma_f32_32x32x2_f32: exact fp32, A/B one
-// value per lane, A[i = l&31][k = l>>5], B[k = l>>5][n = l&31], D column l&31, rows (r&3)+8(r>>2)+4(l>>5)).
+// The decoder is the one dense contraction next to the rasterizer (v_mfma_f32_32x32x2_f32); its tile - operand layouts, the
+// W tile in LDS, phase A - lives in decoder_tile.h, shared with segment.hip.
 
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "decoder_tile.h"
 #include "resize_taps.h"
 
 namespace f3dgs {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- K1: resize into pixel-major X; without a decoder (gt != nullptr) the L1 residual is taken here -------------
 // grid (ceil(N / 64), ceil(C / 32)); LDS tile [32 channels][64 pixels]
@@ -44,18 +43,13 @@ fl_resize_kernel(ResizeGeom g, int C, const float* __restrict__ fm, float* __res
         float loss = 0.f;
         if (p < N) {
             const int yo = p / g.Wg, xo = p - yo * g.Wg;
-            int y0, y1, x0, x1;
-            float ly0, ly1, lx0, lx1;
-            taps(yo, g.sy, g.H, y0, y1, ly0, ly1);
-            taps(xo, g.sx, g.W, x0, x1, lx0, lx1);
+            const PixelTaps tp = pixel_taps(g, yo, xo);
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 const int c = cb + cg * 8 + k;
                 float v = 0.f;
                 if (c < C) {
-                    const float* pl = fm + (size_t)c * g.H * g.W;
-                    v = ly0 * (lx0 * pl[y0 * g.W + x0] + lx1 * pl[y0 * g.W + x1]) +
-                        ly1 * (lx0 * pl[y1 * g.W + x0] + lx1 * pl[y1 * g.W + x1]);
+                    v = bilinear_point(fm + (size_t)c * g.H * g.W, g.W, tp);
                     if (gt) {       // no decoder: residual, loss, gradient w.r.t. the resized map
                         const float r = v - gt[(size_t)c * N + p];
                         loss += fabsf(r);
@@ -86,26 +80,18 @@ fl_resize_kernel(ResizeGeom g, int C, const float* __restrict__ fm, float* __res
 }
 
 // ---- K2: decoder forward + residual + g_x; a WAVE owns 32 pixels for all Cout, a workgroup = 4 waves = 128 pixels ----
-// Everything per pixel stays in registers; the only shared data is the current 32-row tile of W (LDS, double-buffered).
-// With lane l = (px = l & 31, h = l >> 5) and the K index of an MFMA step s defined as c = h C/2 + s (any bijection
-// of K works as long as both operands use it):
-//   phase A   y^T[co][px] = W[co][:] . X[px][:]      A = W tile row (b128 LDS reads: four steps per read),
-//                                                    B = this lane's half row of X, loaded ONCE into C/2 registers
-//   in place  r = y + b - gt,  loss += |r|,  sign byte out,  g = sign(r) / (N Cout)        (accumulator registers)
+//   phase A   y^T[co][px] = W[co][:] . X[px][:] + b[co]                                    (decoder_tile.h)
+//   in place  r = y - gt,  loss += |r|,  sign byte out,  g = sign(r) / (N Cout)            (accumulator registers)
 //   phase B   g_x^T[c][px] += W^T[c][co] g^T[co][px]  A = W tile column (b32 LDS reads), B = the accumulator register r
-//             of phase A itself: D's layout (lane = column px, register r = row co(r, h)) IS the B layout when step r
-//             contracts co(r, 0) with co(r, 1) - no transpose, no LDS round trip, no barrier between the phases.
+//             of phase A itself (decoder_tile.h: D's layout is this contraction's B layout)
 // Per W tile a wave issues C MFMAs and 1.25 LDS reads per MFMA; the decoded (Cout, Hg, Wg) map is never written.
 // (First version: 64 pixels x 128 Cout per workgroup through three LDS tiles of 132 KB - one workgroup of four waves per
 // CU, every operand a 4-byte LDS read behind a barrier: 1.59 ms at 128 -> 512; `profiles/r02_notes.md`.)
 template <int C>
 struct GemmLds {
-    static constexpr int WS = C + 4;          // row stride: 16-byte aligned rows, b128 reads of 32 rows hit all banks evenly
-    float Ws[2][32][WS];
+    float Ws[2][32][decoder_tile::WS<C>];
     float red[4];
 };
-
-__device__ __forceinline__ int mfma_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 D layout
 
 template <int C>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
@@ -114,43 +100,24 @@ fl_decoder_kernel(int N, int Np, int Cout, const float* __restrict__ X, const fl
                   float* __restrict__ loss_partial) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     GemmLds<C>& L = *reinterpret_cast<GemmLds<C>*>(smem);
-    constexpr int NCB = C / 32, HC = C / 2;
-    constexpr int LPT = (32 * C / 4) / 256;       // float4 loads per thread for one W tile (C = 32: 1, 64: 2, 128: 4)
+    namespace dt = decoder_tile;
+    constexpr int NCB = C / 32;
+    constexpr bool LATE_W = dt::LATE_W<C>;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int li = lane & 31, h = lane >> 5;
     const int p = blockIdx.x * 128 + 32 * w + li;
     const bool p_ok = p < N;
-    // this lane's half row of X
-    float xr[HC];
-    {
-        const float4* src = reinterpret_cast<const float4*>(X + (size_t)(p_ok ? p : 0) * C + h * HC);
-#pragma unroll
-        for (int k = 0; k < HC / 4; k++) {
-            const float4 v = src[k];
-            xr[4 * k] = p_ok ? v.x : 0.f; xr[4 * k + 1] = p_ok ? v.y : 0.f; xr[4 * k + 2] = p_ok ? v.z : 0.f; xr[4 * k + 3] = p_ok ? v.w : 0.f;
-        }
-    }
+    float xr[C / 2];
+    dt::load_x<C, true>(xr, X, p, N, h);
     f32x16 gx[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; cb++)
 #pragma unroll
         for (int r = 0; r < 16; r++) gx[cb][r] = 0.f;
     float loss = 0.f;
-    // W tile staging: thread t moves float4 #(t + 256 k) of the 32 x C tile
-    auto load_tile = [&](int co0, float4 (&v)[LPT]) {
-#pragma unroll
-        for (int k = 0; k < LPT; k++) {
-            const int e = (threadIdx.x + 256 * k) * 4, r = e / C, c = e - r * C;
-            v[k] = co0 + r < Cout ? *reinterpret_cast<const float4*>(Wd + (size_t)(co0 + r) * C + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store_tile = [&](int buf, const float4 (&v)[LPT]) {
-#pragma unroll
-        for (int k = 0; k < LPT; k++) {
-            const int e = (threadIdx.x + 256 * k) * 4, r = e / C, c = e - r * C;
-            *reinterpret_cast<float4*>(&L.Ws[buf][r][c]) = v[k];
-        }
-    };
+    constexpr int LPT = dt::LPT<C>;
+    auto load_tile = [&](int co0, float4 (&v)[LPT]) { dt::load_w<C>(v, Wd, Cout, co0); };
+    auto store_tile = [&](int buf, const float4 (&v)[LPT]) { dt::store_w<C>(L.Ws, buf, v); };
     float4 wnext[LPT];
     load_tile(0, wnext);
     store_tile(0, wnext);
@@ -158,14 +125,10 @@ fl_decoder_kernel(int N, int Np, int Cout, const float* __restrict__ X, const fl
     const int ntiles = (Cout + 31) / 32;
     for (int t = 0; t < ntiles; t++) {
         const int co0 = 32 * t, buf = t & 1;
-        // the next W tile: in flight during this tile's MFMAs.  C = 128: requested behind phase A instead (phase B alone is 4 k
-        // matrix-pipe cycles), so that its sixteen registers never live next to the sixteen ground-truth values - together
-        // they put the kernel 21 registers above the 256 of two waves per SIMD (spills inside the tile loop)
-        constexpr bool LATE_W = C >= 128;
         if (!LATE_W && t + 1 < ntiles) load_tile(co0 + 32, wnext);
         // ground truth and bias of this tile's rows, requested before phase A
         float gtv[16];
-        f32x16 acc;                                              // starts at the bias: y = W x + b
+        f32x16 acc;
         // addresses as (wave-uniform row base) + (one 32-bit lane offset shared by the sixteen rows): row(r, h) = row(r, 0) + 4 h,
         // so the lane-dependent part, 4 h N + p, does not depend on r (sixteen 64-bit per-lane addresses - and sixteen more for
         // the sign bytes below - would otherwise be kept in registers across the tile)
@@ -176,20 +139,9 @@ fl_decoder_kernel(int N, int Np, int Cout, const float* __restrict__ X, const fl
             const bool ok = p_ok && co < Cout;
             const float* grow = gt + (size_t)(co0 + mfma_row(r, 0)) * N;      // uniform
             gtv[r] = ok ? grow[gt_lane] : 0.f;
-            acc[r] = co < Cout ? bias[co] : 0.f;
+            acc[r] = dt::bias_row(bias, Cout, co);                   // (one loop with the ground truth: they share the row guard)
         }
-        // ---- phase A (scheduling fences: without them every LDS read of the unrolled loop is hoisted to the top and
-        //      the kernel needs > 256 registers)
-        const float* wrow = &L.Ws[buf][li][h * HC];
-#pragma unroll
-        for (int s4 = 0; s4 < HC / 4; s4++) {
-            const float4 a = *reinterpret_cast<const float4*>(wrow + 4 * s4);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, xr[4 * s4 + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, xr[4 * s4 + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, xr[4 * s4 + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, xr[4 * s4 + 3], acc, 0, 0, 0);
-            if ((s4 & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-        }
+        dt::phase_a<C>(acc, L.Ws, buf, li, h, xr);
         // ---- residual, loss, sign, g (in place)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
@@ -241,35 +193,16 @@ fl_decode_kernel(int N, int Cout, const float* __restrict__ X, const float* __re
                  void* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     GemmLds<C>& L = *reinterpret_cast<GemmLds<C>*>(smem);
-    constexpr int HC = C / 2;
-    constexpr int LPT = (32 * C / 4) / 256;
+    namespace dt = decoder_tile;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int li = lane & 31, h = lane >> 5;
     const int p = blockIdx.x * 128 + 32 * w + li;
     const bool p_ok = p < N;
-    float xr[HC];
-    {
-        const float4* src = reinterpret_cast<const float4*>(X + (size_t)(p_ok ? p : 0) * C + h * HC);
-#pragma unroll
-        for (int k = 0; k < HC / 4; k++) {
-            const float4 v = src[k];
-            xr[4 * k] = v.x; xr[4 * k + 1] = v.y; xr[4 * k + 2] = v.z; xr[4 * k + 3] = v.w;
-        }
-    }
-    auto load_tile = [&](int co0, float4 (&v)[LPT]) {
-#pragma unroll
-        for (int k = 0; k < LPT; k++) {
-            const int e = (threadIdx.x + 256 * k) * 4, r = e / C, c = e - r * C;
-            v[k] = co0 + r < Cout ? *reinterpret_cast<const float4*>(Wd + (size_t)(co0 + r) * C + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto store_tile = [&](int buf, const float4 (&v)[LPT]) {
-#pragma unroll
-        for (int k = 0; k < LPT; k++) {
-            const int e = (threadIdx.x + 256 * k) * 4, r = e / C, c = e - r * C;
-            *reinterpret_cast<float4*>(&L.Ws[buf][r][c]) = v[k];
-        }
-    };
+    float xr[C / 2];
+    dt::load_x<C, false>(xr, X, p, N, h);
+    constexpr int LPT = dt::LPT<C>;
+    auto load_tile = [&](int co0, float4 (&v)[LPT]) { dt::load_w<C>(v, Wd, Cout, co0); };
+    auto store_tile = [&](int buf, const float4 (&v)[LPT]) { dt::store_w<C>(L.Ws, buf, v); };
     float4 wnext[LPT];
     load_tile(0, wnext);
     store_tile(0, wnext);
@@ -277,23 +210,10 @@ fl_decode_kernel(int N, int Cout, const float* __restrict__ X, const float* __re
     const int ntiles = (Cout + 31) / 32;
     for (int t = 0; t < ntiles; t++) {
         const int co0 = 32 * t, buf = t & 1;
-        if (t + 1 < ntiles) load_tile(co0 + 32, wnext);
+        if (t + 1 < ntiles) load_tile(co0 + 32, wnext);     // (no LATE_W: nothing else lives through phase A here)
         f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int co = co0 + mfma_row(r, h);
-            acc[r] = co < Cout ? bias[co] : 0.f;
-        }
-        const float* wrow = &L.Ws[buf][li][h * HC];
-#pragma unroll
-        for (int s4 = 0; s4 < HC / 4; s4++) {
-            const float4 a = *reinterpret_cast<const float4*>(wrow + 4 * s4);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, xr[4 * s4 + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, xr[4 * s4 + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, xr[4 * s4 + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, xr[4 * s4 + 3], acc, 0, 0, 0);
-            if ((s4 & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-        }
+        dt::bias_start(acc, bias, Cout, co0, h);
+        dt::phase_a<C>(acc, L.Ws, buf, li, h, xr);
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int co = co0 + mfma_row(r, h);
@@ -315,16 +235,12 @@ fl_resize_out_kernel(ResizeGeom g, int C, const float* __restrict__ fm, void* __
     const int p = blockIdx.x * 64 + (threadIdx.x & 63), cg = threadIdx.x >> 6;
     if (p >= N) return;
     const int yo = p / g.Wg, xo = p - yo * g.Wg;
-    int y0, y1, x0, x1;
-    float ly0, ly1, lx0, lx1;
-    taps(yo, g.sy, g.H, y0, y1, ly0, ly1);
-    taps(xo, g.sx, g.W, x0, x1, lx0, lx1);
+    const PixelTaps tp = pixel_taps(g, yo, xo);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int c = blockIdx.y * 32 + cg * 8 + k;
         if (c >= C) continue;
-        const float* pl = fm + (size_t)c * g.H * g.W;
-        const float v = ly0 * (lx0 * pl[y0 * g.W + x0] + lx1 * pl[y0 * g.W + x1]) + ly1 * (lx0 * pl[y1 * g.W + x0] + lx1 * pl[y1 * g.W + x1]);
+        const float v = bilinear_point(fm + (size_t)c * g.H * g.W, g.W, tp);
         if constexpr (HALF) reinterpret_cast<__half*>(out)[(size_t)c * N + p] = __float2half_rn(v);
         else reinterpret_cast<float*>(out)[(size_t)c * N + p] = v;
     }
@@ -533,8 +449,7 @@ __global__ void __launch_bounds__(256) fl_sum_kernel(const float* __restrict__ p
     __shared__ double sh[4];
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) acc += (double)partial[i];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) *out = (float)(sh[0] + sh[1] + sh[2] + sh[3]);

@@ -25,12 +25,11 @@
 #include <math.h>
 
 #include "common.h"
+#include "decoder_tile.h"      // f32x16, mfma_row (the tiling here is its own)
 
 namespace f3dgs {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int PB = 64;           // channel block edge of a workgroup
 constexpr int PK = 64;           // samples per stage
@@ -39,8 +38,6 @@ constexpr int PFLUSH = 4;        // stages between two float64 flushes of the ac
 constexpr int PSLAB = 1024;      // shortest slab (samples)
 constexpr int PMAX_GROUPS = 1024;    // workgroups of the Gram kernel beyond which slabs grow instead
 constexpr int PCHUNK = 16384;    // samples per workgroup of pca_sum_kernel
-
-__device__ __forceinline__ int mfma_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 D layout
 
 struct PcaGeom {
     size_t n;            // samples
@@ -106,8 +103,7 @@ __global__ void __launch_bounds__(256) pca_sum_kernel(int C, size_t HW, size_t n
     const float* src = fm + (size_t)c * HW;
     double acc = 0.0;
     for (size_t s = s0 + threadIdx.x; s < s1; s += 256) acc += (double)(src[s * stride] * inv[s]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) part[(size_t)blockIdx.x * C + c] = ((red[0] + red[1]) + red[2]) + red[3];
@@ -255,8 +251,7 @@ __global__ void __launch_bounds__(256) pca_project_kernel(int C, size_t HW, cons
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) m[k] += __shfl_xor(m[k], d, 64);
+        m[k] = wave_sum(m[k]);
         if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = m[k];
     }
     __syncthreads();

@@ -439,12 +439,6 @@ __global__ void __launch_bounds__(256) merge_adjacency_kernel(MergeGraph g, uint
     if (!(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(word, bit);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // one wave per row a of the matrix: its set bits are the groups b > a adjacent to a
 __global__ void __launch_bounds__(256) merge_unite_kernel(int G, int C, int words, const uint32_t* __restrict__ bits,
                                                           const float* __restrict__ fm, float min_cos, int32_t* __restrict__ parent,
@@ -470,9 +464,9 @@ __global__ void __launch_bounds__(256) merge_unite_kernel(int G, int C, int word
                     aa += x * x;
                     bb += y * y;
                 }
-                ab = wave_sum_f64(ab);
-                aa = wave_sum_f64(aa);
-                bb = wave_sum_f64(bb);
+                ab = wave_sum(ab);
+                aa = wave_sum(aa);
+                bb = wave_sum(bb);
                 if (lane == 0 && aa > 0.0 && bb > 0.0 && ab / sqrt(aa * bb) >= (double)min_cos) unite(parent, a, b, G, status);
             }
         }

@@ -59,12 +59,6 @@ struct InstScratch {
     }
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // T = 0; with `outputs` (P == 0) also what a match over an empty table gives: every mask unmatched
 __global__ void __launch_bounds__(INST_BLOCK) inst_fill_kernel(size_t n, float* __restrict__ T, size_t n_rest, float* __restrict__ rest, int M,
                                                                int outputs, int* __restrict__ mapping, int* __restrict__ best_label,
@@ -151,7 +145,7 @@ __global__ void __launch_bounds__(INST_BLOCK) inst_sums_kernel(int M, int L, int
         const float* t = T + (size_t)m * (L + 1);
         double s = 0.0;
         for (int l = lane; l < L; l += 64) s += (double)t[l];
-        s = wave_sum_f64(s);
+        s = wave_sum(s);
         if (lane == 0) {
             sc.row[m] = s;
             sc.rowall[m] = s + (double)t[L];

@@ -78,27 +78,6 @@ __device__ __forceinline__ long long total_runs(const int32_t* hdr) { return *re
 __device__ __forceinline__ int col_begin(const Runs& r, const Shape& s, int k, int x) { return r.base[k] + r.local[(size_t)k * s.FW + x]; }
 __device__ __forceinline__ int col_end(const Runs& r, const Shape& s, int k, int x) { return x + 1 < s.FW ? col_begin(r, s, k, x + 1) : r.base[k + 1]; }
 
-// exclusive prefix of v over the 256 threads, and the sum
-template <typename T>
-__device__ __forceinline__ T block_scan(T v, T* s_w, T& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    T before = 0;
-    total = 0;
-    for (int w = 0; w < 4; w++) {
-        if (w < wave) before += s_w[w];
-        total += s_w[w];
-    }
-    return before + inc - v;
-}
-
 __global__ void __launch_bounds__(256) regions_count_kernel(Shape s, const uint32_t* __restrict__ packed, const int32_t* __restrict__ index,
                                                             int holes, int32_t* __restrict__ local, int32_t* __restrict__ totals) {
     __shared__ int s_w[4];

@@ -1,6 +1,7 @@
 // resize_taps.h - the bilinear resize of the feature-map loss (F.interpolate(mode='bilinear', align_corners=True),
 // R/train.py:99-101) as per-axis tap lists, shared by the loss kernels (feature_loss.hip) and by the blend backward when it
-// takes the loss's gradient at the LOSS's resolution (render_bwd_pl.hip, f3dgs_set_feature_grad_lowres).
+// takes the loss's gradient at the LOSS's resolution (render_bwd_pl.hip, f3dgs_set_feature_grad_lowres), and the bilinear
+// point itself, shared by the loss, the decode and the segmentation (segment.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,6 +28,30 @@ __device__ __forceinline__ void taps(int o, float scale, int in, int& i0, int& i
     i1 = i0 + (i0 < in - 1 ? 1 : 0);
     l1 = src - (float)i0;
     l0 = 1.0f - l1;
+}
+
+// the taps of output pixel (yo, xo) along both axes
+struct PixelTaps {
+    int y0, y1, x0, x1;
+    float ly0, ly1, lx0, lx1;
+};
+
+__device__ __forceinline__ PixelTaps pixel_taps(const ResizeGeom& g, int yo, int xo) {
+    PixelTaps t;
+    taps(yo, g.sy, g.H, t.y0, t.y1, t.ly0, t.ly1);
+    taps(xo, g.sx, g.W, t.x0, t.x1, t.lx0, t.lx1);
+    return t;
+}
+
+// The bilinear point from its four source values v<row><column>: THE order of operations of the resize - the decode, the loss
+// and the segmentation promise each other the same bits, so nobody writes this expression out again
+__device__ __forceinline__ float bilinear_mix(const PixelTaps& t, float v00, float v01, float v10, float v11) {
+    return t.ly0 * (t.lx0 * v00 + t.lx1 * v01) + t.ly1 * (t.lx0 * v10 + t.lx1 * v11);
+}
+
+// ... of a plane of row width W
+__device__ __forceinline__ float bilinear_point(const float* pl, int W, const PixelTaps& t) {
+    return bilinear_mix(t, pl[t.y0 * W + t.x0], pl[t.y0 * W + t.x1], pl[t.y1 * W + t.x0], pl[t.y1 * W + t.x1]);
 }
 
 // candidate outputs of a source index i: outputs o whose taps can include i.

@@ -374,26 +374,6 @@ __global__ void __launch_bounds__(256) rle_count_kernel(int FH, int FW, int NW, 
     if (threadIdx.x == 0) lens[blockIdx.x] = s_n + 1 + (int)(pm[0] & 1u);
 }
 
-// exclusive prefix of v over the 256 threads, and the sum
-__device__ __forceinline__ int block_scan(int v, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-    for (int w = 0; w < 4; w++) {
-        if (w < wave) before += s_w[w];
-        total += s_w[w];
-    }
-    return before + inc - v;
-}
-
 __global__ void __launch_bounds__(256) rle_emit_kernel(int FH, int FW, int NW, const uint32_t* __restrict__ packed,
                                                        const int32_t* __restrict__ index, const int32_t* __restrict__ lens,
                                                        const int64_t* __restrict__ ends, int64_t capacity, int32_t* __restrict__ out) {
@@ -414,7 +394,7 @@ __global__ void __launch_bounds__(256) rle_emit_kernel(int FH, int FW, int NW, c
         const int x = q / NW, wy = q - x * NW;
         uint32_t tw = q < words ? transitions(pm, x, wy, NW, FH) : 0u;
         int total;
-        int at = rank + block_scan(__popc(tw), s_w, total);
+        int at = rank + block_scan((int)__popc(tw), s_w, total);
         for (; tw; tw &= tw - 1u) {
             if (at < n) o[at] = x * FH + 32 * wy + (int)__builtin_ctz(tw);       // (at < n always: the bound guards the store)
             at++;

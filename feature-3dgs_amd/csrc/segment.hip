@@ -14,7 +14,7 @@
 //   fl_resize_kernel  (feature_loss.hip, with a decoder only) the resized map, pixel-major X[N][C]: the decode's own kernel,
 //                     so the decoded values below are those of f3dgs_feature_decode bit for bit
 //   seg_kernel        a WAVE owns 32 pixels, a workgroup = 4 waves = 128 pixels.  Per 32-row block of the decoder:
-//     phase A   D^T[co][px] = W[co][:] . X[px][:] + b[co]   exactly fl_decode_kernel's loop (same operands, same order);
+//     phase A   D^T[co][px] = W[co][:] . X[px][:] + b[co]   fl_decode_kernel's loop itself (decoder_tile.h: one copy for both);
 //               without a decoder the block is the resized map itself, taken from the source map with fl_resize_out_kernel's
 //               expression, in the accumulator's layout
 //     in place  ROUND_HALF: every value to IEEE fp16 and back;  ss += D^2
@@ -29,13 +29,12 @@
 #include <math.h>
 
 #include "common.h"
+#include "decoder_tile.h"
 #include "resize_taps.h"
 
 namespace f3dgs {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int SEG_TS = 36;     // text tile row stride: 32 columns + one b128 of padding, so that the b128 reads of 32 rows hit all banks evenly
 
@@ -54,8 +53,6 @@ struct SegArgs {
     int64_t* labels;
     float* score;              // or nullptr
 };
-
-__device__ __forceinline__ int mfma_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 D layout
 
 __device__ __forceinline__ float round_h(float x) { return __half2float(__float2half_rn(x)); }
 
@@ -89,18 +86,18 @@ template <int C, int NKB>
 constexpr int seg_waves() { return ((C == 0 || C >= 128) && NKB > 5) || NKB > 6 ? 1 : 2; }
 
 template <int C, int NKB>
-constexpr size_t seg_lds_bytes() { return sizeof(float) * (2 * 32 * NKB * SEG_TS + (C ? 2 * 32 * (C + 4) : 0)); }
+constexpr size_t seg_lds_bytes() { return sizeof(float) * (2 * 32 * NKB * SEG_TS + (C ? 2 * 32 * decoder_tile::WS<C> : 0)); }
 
 template <int C, int NKB>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(seg_waves<C, NKB>())))
 seg_kernel(const SegArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr bool DEC = C > 0;
-    constexpr int WS = C + 4;                  // W tile row stride (GemmLds of feature_loss.hip)
+    namespace dt = decoder_tile;
     constexpr int HC = DEC ? C / 2 : 1;
-    constexpr int LPT = DEC ? (32 * C / 4) / 256 : 1;      // float4 per thread for one W tile
+    constexpr int LPT = DEC ? dt::LPT<C> : 1;              // float4 per thread for one W tile
     float* const Ts = reinterpret_cast<float*>(smem);      // [2][32 NKB][SEG_TS]
-    float* const Ws = Ts + 2 * 32 * NKB * SEG_TS;          // [2][32][WS]
+    float* Ws = Ts + 2 * 32 * NKB * SEG_TS;                // the decoder's W tiles (decoder_tile.h)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int li = lane & 31, h = lane >> 5;
     const int N = a.N, Cout = a.Cout;
@@ -134,44 +131,25 @@ seg_kernel(const SegArgs a) {
             *reinterpret_cast<float4*>(Ts + ((size_t)buf * 32 * NKB + k) * SEG_TS + c) = v[j];
         }
     };
-    // W tile staging, as fl_decode_kernel
+    // W tile staging (nothing without a decoder)
     auto load_w = [&](int co0, float4 (&v)[LPT]) {
-        if constexpr (DEC) {
-#pragma unroll
-            for (int k = 0; k < LPT; k++) {
-                const int e = (threadIdx.x + 256 * k) * 4, r = e / C, c = e - r * C;
-                v[k] = co0 + r < Cout ? *reinterpret_cast<const float4*>(a.Wd + (size_t)(co0 + r) * C + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
+        if constexpr (DEC) dt::load_w<C>(v, a.Wd, Cout, co0);
     };
     auto store_w = [&](int buf, const float4 (&v)[LPT]) {
-        if constexpr (DEC) {
-#pragma unroll
-            for (int k = 0; k < LPT; k++) {
-                const int e = (threadIdx.x + 256 * k) * 4, r = e / C, c = e - r * C;
-                *reinterpret_cast<float4*>(Ws + ((size_t)buf * 32 + r) * WS + c) = v[k];
-            }
-        }
+        if constexpr (DEC) dt::store_w<C>(Ws, buf, v);
     };
 
     // with a decoder: this lane's half row of X.  Without: the lane's taps into the source map
     float xr[HC];
     uint32_t o00 = 0, o01 = 0, o10 = 0, o11 = 0;
-    float ly0 = 0.f, ly1 = 0.f, lx0 = 0.f, lx1 = 0.f;
+    PixelTaps tp = {};
     if constexpr (DEC) {
-        const float4* src = reinterpret_cast<const float4*>(a.X + (size_t)(p_ok ? p : 0) * C + h * HC);
-#pragma unroll
-        for (int k = 0; k < HC / 4; k++) {
-            const float4 v = src[k];
-            xr[4 * k] = v.x; xr[4 * k + 1] = v.y; xr[4 * k + 2] = v.z; xr[4 * k + 3] = v.w;
-        }
+        dt::load_x<C, false>(xr, a.X, p, N, h);
     } else {
         const int pp = p_ok ? p : 0;
         const int yo = pp / a.g.Wg, xo = pp - yo * a.g.Wg;
-        int y0, y1, x0, x1;
-        taps(yo, a.g.sy, a.g.H, y0, y1, ly0, ly1);
-        taps(xo, a.g.sx, a.g.W, x0, x1, lx0, lx1);
-        o00 = y0 * a.g.W + x0; o01 = y0 * a.g.W + x1; o10 = y1 * a.g.W + x0; o11 = y1 * a.g.W + x1;
+        tp = pixel_taps(a.g, yo, xo);
+        o00 = tp.y0 * a.g.W + tp.x0; o01 = tp.y0 * a.g.W + tp.x1; o10 = tp.y1 * a.g.W + tp.x0; o11 = tp.y1 * a.g.W + tp.x1;
     }
     // addresses as (wave-uniform channel plane) + (one 32-bit lane offset per tap): channel(r, h) = channel(r, 0) + 4 h, so the
     // lane-dependent part does not depend on r (sixty-four 64-bit per-lane addresses would otherwise be formed per block)
@@ -186,8 +164,7 @@ seg_kernel(const SegArgs a) {
             const float* pl = a.fm + (size_t)(cu < a.C ? cu : 0) * plane;         // uniform
             const uint32_t ho = ok ? hp : 0u;
             // (the taps of an identity resize have weights 1, 0, 0, 0, and 0 * inf of a neighbour would make this pixel NaN)
-            const float val = a.identity ? pl[ho + o00]
-                                         : ly0 * (lx0 * pl[ho + o00] + lx1 * pl[ho + o01]) + ly1 * (lx0 * pl[ho + o10] + lx1 * pl[ho + o11]);
+            const float val = a.identity ? pl[ho + o00] : bilinear_mix(tp, pl[ho + o00], pl[ho + o01], pl[ho + o10], pl[ho + o11]);
             v[r] = ok ? val : 0.f;
         }
     };
@@ -214,22 +191,10 @@ seg_kernel(const SegArgs a) {
         const bool more = t + 1 < ntiles;
         f32x16 acc;
         if constexpr (DEC) {
-            // C = 128: the next W tile is requested behind phase A, so that its registers do not live through it
-            constexpr bool LATE_W = C >= 128;
+            constexpr bool LATE_W = dt::LATE_W<C>;
             if (!LATE_W && more) load_w(co0 + 32, wnext);
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[r] = a.bias[co0 + mfma_row(r, h)];          // Cout % 32 == 0 with a decoder
-            // ---- phase A: fl_decode_kernel's loop
-            const float* wrow = Ws + ((size_t)buf * 32 + li) * WS + h * HC;
-#pragma unroll
-            for (int s4 = 0; s4 < HC / 4; s4++) {
-                const float4 av = *reinterpret_cast<const float4*>(wrow + 4 * s4);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, xr[4 * s4 + 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, xr[4 * s4 + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, xr[4 * s4 + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, xr[4 * s4 + 3], acc, 0, 0, 0);
-                if ((s4 & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-            }
+            dt::bias_start<true>(acc, a.bias, Cout, co0, h);          // Cout % 32 == 0 with a decoder
+            dt::phase_a<C>(acc, Ws, buf, li, h, xr);                  // fl_decode_kernel's, call for call
             if (LATE_W && more) load_w(co0 + 32, wnext);
         } else {
 #pragma unroll

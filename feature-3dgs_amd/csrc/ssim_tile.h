@@ -161,8 +161,7 @@ __device__ __forceinline__ T four_wave_sum(const T* v) {
 }
 
 __device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    v = wave_sum(v);
     __syncthreads();            // (sh is re-used from one call to the next)
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -104,7 +104,7 @@ def test_reference_chain_narrower_and_wider_than_the_segmentation_size(gt_size):
     O.judge(labels, l64, tau)
 
 
-@pytest.mark.parametrize("name", ["dec32_k20", "dec128_k150"])
+@pytest.mark.parametrize("name", ["dec32_k20", "dec64_k1", "dec128_k150"])
 def test_decoded_map_gives_exactly_the_fused_labels(name):
     """segment() on the stored map of fused_feature_decode(half=True) == segment() with the decoder fused: the same decode,
     the same rounding, the same contraction order"""
