@@ -303,6 +303,7 @@ const OptionDesc kOptions[] = {
     {"fwd_wide", "F3DGS_FWD_WIDE", &Options::fwd_wide, 1},
     {"fwd_solo", "F3DGS_FWD_SOLO", &Options::fwd_solo, 1},
     {"sort_onesweep", "F3DGS_SORT_ONESWEEP", &Options::sort_onesweep, 0},
+    {"depth_sort_buckets", "F3DGS_DEPTH_SORT_BUCKETS", &Options::depth_sort_buckets, -1},
     {"sync_free", "F3DGS_SYNC_FREE", &Options::sync_free, -1},
     {"instance_capacity", "F3DGS_INSTANCE_CAPACITY", &Options::instance_capacity, 0},
     {"knn_outward", "F3DGS_KNN_OUTWARD", &Options::knn_outward, 1},
@@ -349,6 +350,7 @@ namespace {
 struct CountReadback {
     uint32_t* host = nullptr;       // host address (read by this thread): [0] entries of our lists, [1] the reference's count, [2] long-axis flag (kernel-written);
                                     // [3] entries the last enqueued frame provided for (host-written); [4] sticky: an emit wave of a sync-free frame found no room (kernel-written, cleared by f3dgs_forward_counts)
+                                    // [5] largest bucket, [6] buckets above the capacity of the frame's depth sort by buckets (kernel-written; f3dgs_depth_sort_info)
     uint32_t* dev = nullptr;        // the same words as the current device sees them (written by a kernel)
     hipEvent_t done = nullptr;
     int device = -1;
@@ -360,6 +362,9 @@ struct CountReadback {
 struct CountHint { bool known = false; uint32_t own = 0, ref = 0; };
 thread_local CountHint g_count_hint[64];
 thread_local const uint32_t* g_last_forward_words = nullptr;
+thread_local f3dgs::DepthSortInfo g_last_depth_sort = {F3DGS_DEPTH_SORT_NONE, 0u, 0u};      // (f3dgs_depth_sort_info)
+thread_local bool g_depth_sort_known = false;
+thread_local uint32_t g_depth_sort_words[5];
 bool stream_is_capturing(hipStream_t s) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -423,6 +428,18 @@ int f3dgs_version(void) { return 32200; }   // 3.22.0 (major * 10000 + minor * 1
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 
 const uint32_t* f3dgs_forward_counts(void) { return g_last_forward_words; }
+
+const uint32_t* f3dgs_depth_sort_info(void) {
+    if (!g_depth_sort_known) return nullptr;
+    const bool bk = g_last_depth_sort.path == F3DGS_DEPTH_SORT_BUCKETS && g_last_forward_words;
+    const volatile uint32_t* w = g_last_forward_words;      // (kernel-written pinned words)
+    g_depth_sort_words[0] = (uint32_t)g_last_depth_sort.path;
+    g_depth_sort_words[1] = g_last_depth_sort.buckets;
+    g_depth_sort_words[2] = g_last_depth_sort.capacity;
+    g_depth_sort_words[3] = bk ? w[5] : 0u;
+    g_depth_sort_words[4] = bk ? w[6] : 0u;
+    return g_depth_sort_words;
+}
 
 int f3dgs_set_option(const char* name, int value) {
     if (!name) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null option name");
@@ -606,8 +623,15 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
     const OffsetSumsJob sums = {geom.tiles_touched, geom.scan_tmp, geom.scan_sub};
     bool sums_done = false;         // small scenes: the one-workgroup depth sort leaves the list-offset sums as well
     bool counts_in_a = false;       // the multi-launch depth sort leaves the tile counts in depth order in key_a (GeomState::key_a)
+    // more than SMALL_SORT_MAX Gaussians: one bucket pass and an in-LDS sort per bucket, or LSD passes (option depth_sort_buckets)
+    const int bk_opt = options().depth_sort_buckets;
+    const bool buckets = bk_opt > 0 || (bk_opt < 0 && (size_t)P > DEPTH_BUCKET_AUTO_ABOVE && (size_t)P <= DEPTH_BUCKET_AUTO_UPTO);
+    DepthSortInfo sort_info = {F3DGS_DEPTH_SORT_LOOKBACK, 0u, 0u};
     if (onesweep) launch_depth_sort_onesweep(geom, (size_t)P, s);
-    else HIP_TRY(launch_depth_sort(geom.depth_key, geom.key_a, geom.val_a, geom.key_b, geom.val_b, (size_t)P, geom.hist, &tj, s, &sums, &sums_done, &counts_in_a));
+    else HIP_TRY(launch_depth_sort(geom.depth_key, geom.key_a, geom.val_a, geom.key_b, geom.val_b, (size_t)P, geom.hist, &tj, s, &sums, &sums_done, &counts_in_a,
+                                   buckets, rb.dev + 5, &sort_info));
+    g_last_depth_sort = sort_info;
+    g_depth_sort_known = true;
     if ((rc = check_debug(debug, s, "depth sort"))) return rc;
     tm.mark("depth_sort");
     const uint32_t* order = geom.val_a;

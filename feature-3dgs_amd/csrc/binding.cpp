@@ -1350,6 +1350,20 @@ PYBIND11_MODULE(_C, m) {
         return py::make_tuple((long long)v[0], (long long)v[1], (long long)v[2], (long long)v[3], (long long)v[4]);
     }, "(entries of the instance lists, the reference's num_rendered, long-axis flag, entries provided for, sticky no-room word) of the "
        "calling thread's most recent forward call - final once that frame's work has completed; None before the first call");
+    m.def("depth_sort_info", []() -> py::object {
+        const uint32_t* w = f3dgs_depth_sort_info();
+        if (!w) return py::none();
+        py::dict d;
+        static const char* const names[] = {"none", "one_launch", "passes", "buckets", "lookback"};
+        d["path"] = w[0] < 5 ? names[w[0]] : "?";
+        d["buckets"] = (long long)w[1];
+        d["capacity"] = (long long)w[2];
+        d["largest"] = (long long)w[3];
+        d["oversized"] = (long long)w[4];
+        return d;
+    }, "how the calling thread's most recent forward call sorted its Gaussians by depth: path ('one_launch', 'passes', 'buckets', "
+       "'lookback', 'none'), and of the bucket path the bins in use, the in-LDS capacity of a bucket, the frame's largest bucket and "
+       "its buckets above the capacity (the last two final once the frame's work has completed); None before the first call");
     m.def("forward_counts_address", []() { return (uintptr_t)f3dgs_forward_counts(); },
           "host address of the five uint32 words of forward_counts() (0 before the first call): a captured step keeps it and reads the words after a replay");
     m.def("clear_forward_overflow", [](uintptr_t address) { if (address) reinterpret_cast<volatile uint32_t*>(address)[4] = 0u; },

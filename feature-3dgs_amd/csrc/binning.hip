@@ -5,7 +5,8 @@
 // stable-sort all N pairs on the 64-bit key with cub (6 passes at 1080p), find per-tile ranges.
 //
 // What this file does instead (same resulting order, far less traffic):
-//   1. stable sort of the P Gaussians by their 32-bit depth key (4 passes over P pairs);
+//   1. stable sort of the P Gaussians by their 32-bit depth key (4 LSD passes over P pairs - or one bucket pass and one launch
+//      that sorts every bucket inside LDS: "depth sort by buckets" below);
 //   2. prefix-sum of tiles_touched taken IN DEPTH ORDER;
 //   3. emit instances (tile, id) in depth order;
 //   4. stable sort of the N instances by tile id only (2 passes at <= 65536 tiles, digits as wide as the tile count needs).
@@ -97,11 +98,19 @@ __device__ __forceinline__ void run_totals_job(const TotalsJob& tj) {
     }
 }
 
-template <int BITS, int ITEMS>
+// BUCKET (the bucket pass of the depth sort, common.h): the digit of a key is its bucket, (key - kmin) >> s, the last bin for the
+// culled keys.  kmin / kmax are the extremes of preprocess_kernel's per-workgroup partials (tj.partial: the fourth and fifth
+// run), which EVERY workgroup reduces for itself - a few KB out of L2, behind its keys' requests - so that no launch stands
+// between preprocess and this one; workgroup 0 leaves kmin and s in ctl[0 .. 1] for the two launches that follow.
+__device__ __forceinline__ uint32_t depth_bucket_of(uint32_t key, uint32_t kmin, uint32_t s, uint32_t culled_bin) {
+    return key == 0xFFFFFFFFu ? culled_bin : (key - kmin) >> s;
+}
+template <int BITS, int ITEMS, bool BUCKET = false>
 __global__ void __launch_bounds__(SORT_THREADS) radix_hist_kernel(const uint32_t* __restrict__ keys, size_t n,
                                                                   int shift, uint32_t nb,
                                                                   uint32_t* __restrict__ hist, TotalsJob tj,
-                                                                  const uint32_t* __restrict__ n_dev) {
+                                                                  const uint32_t* __restrict__ n_dev, uint32_t bucket_count,
+                                                                  uint32_t* __restrict__ ctl) {
     constexpr int BINS = 1 << BITS;
     constexpr int CHUNK = SORT_THREADS * ITEMS;
     __shared__ uint32_t h[BINS];
@@ -119,12 +128,34 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_hist_kernel(const uint32_t
         key[k] = i < n ? keys[i] : 0u;
     }
     if (tj.partial && blockIdx.x == 0) run_totals_job<SORT_THREADS>(tj);
+    uint32_t kmin = 0, bshift = 0;
+    if constexpr (BUCKET) {
+        __shared__ uint32_t shk[2][SORT_THREADS / 64];
+        uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+        for (int i = threadIdx.x; i < tj.n_partial; i += SORT_THREADS) {
+            lo = min(lo, tj.partial[3 * tj.n_partial + i]);
+            hi = max(hi, tj.partial[4 * tj.n_partial + i]);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            lo = min(lo, (uint32_t)__shfl_xor((int)lo, d, 64));
+            hi = max(hi, (uint32_t)__shfl_xor((int)hi, d, 64));
+        }
+        if ((threadIdx.x & 63) == 0) { shk[0][threadIdx.x >> 6] = lo; shk[1][threadIdx.x >> 6] = hi; }
+        __syncthreads();
+        lo = min(min(shk[0][0], shk[0][1]), min(shk[0][2], shk[0][3]));
+        hi = max(max(shk[1][0], shk[1][1]), max(shk[1][2], shk[1][3]));
+        kmin = lo;
+        bshift = depth_bucket_shift(lo, hi, bucket_count);
+        if (blockIdx.x == 0 && threadIdx.x == 0) { ctl[0] = kmin; ctl[1] = bshift; }
+    }
     for (int d = threadIdx.x; d < BINS; d += SORT_THREADS) h[d] = 0;
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
         const size_t i = base + (size_t)k * SORT_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&h[(key[k] >> shift) & (BINS - 1)], 1u);
+        const uint32_t d = BUCKET ? depth_bucket_of(key[k], kmin, bshift, BINS - 1) : (key[k] >> shift) & (BINS - 1);
+        if (i < n) atomicAdd(&h[d], 1u);
     }
     __syncthreads();
     for (int d = threadIdx.x; d < BINS; d += SORT_THREADS) hist[(size_t)d * nb + blockIdx.x] = h[d];  // digit-major
@@ -187,15 +218,23 @@ __device__ __forceinline__ void record_range(uint2* ranges_enc, uint32_t tile, b
 // COUNTS (final pass of the depth sort): nobody reads that pass's sorted keys, so an item's slot of keys_out receives
 // payload[value] instead - the Gaussian's tile count at its place in the depth order (GeomState::key_a), gathered here, where
 // the id is in a register anyway, rather than by the two kernels that walk the order afterwards.  The same stores, no more LDS.
-template <int BITS, int ITEMS, bool REORDER, bool RANGES, bool COUNTS = false>
+// BUCKET (see radix_hist_kernel; never with REORDER): the digit is the key's bucket by ctl[0 .. 1], and workgroup 0 leaves every
+// bucket's first position in bucket_offs for the launch that sorts the buckets.
+template <int BITS, int ITEMS, bool REORDER, bool RANGES, bool COUNTS = false, bool BUCKET = false>
 __global__ void __launch_bounds__(SORT_THREADS)
 radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                      uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out, size_t n, int shift,
                      uint32_t nb, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ totals,
                      uint2* __restrict__ ranges_enc, const uint32_t* __restrict__ n_dev,
-                     const uint32_t* __restrict__ payload) {
+                     const uint32_t* __restrict__ payload, const uint32_t* __restrict__ ctl, uint32_t* __restrict__ bucket_offs) {
     constexpr int BINS = 1 << BITS;
     constexpr int CHUNK = SORT_THREADS * ITEMS;
+    static_assert(!(BUCKET && (REORDER || RANGES || COUNTS)), "the bucket pass is a plain scatter of keys and ids");
+    const uint32_t bk_min = BUCKET ? ctl[0] : 0u, bk_shift = BUCKET ? ctl[1] : 0u;
+    auto digit_of = [&](uint32_t key) -> uint32_t {
+        if constexpr (BUCKET) return depth_bucket_of(key, bk_min, bk_shift, BINS - 1);
+        else return (key >> shift) & (BINS - 1);
+    };
     // bins per thread in the offset phase; fewer bins than threads (digits of 4 ... 7 bits): the first BINS threads own one each
     constexpr int BPT = BINS >= SORT_THREADS ? BINS / SORT_THREADS : 1;
     static_assert(BINS >= SORT_THREADS ? BINS % SORT_THREADS == 0 : true, "whole bins per thread");
@@ -235,7 +274,7 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
     for (int k = 0; k < ITEMS; k++) {
         const size_t i = wbase + (size_t)k * 64 + lane;
         const bool valid = i < n;
-        const uint32_t d = (key[k] >> shift) & (BINS - 1);
+        const uint32_t d = digit_of(key[k]);
         const unsigned long long vm = __ballot(valid);
         uint32_t p_lo = (uint32_t)vm, p_hi = (uint32_t)(vm >> 32);
 #pragma unroll
@@ -284,6 +323,7 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
             const uint32_t d = threadIdx.x * BPT + q;
             if (BINS < SORT_THREADS && d >= (uint32_t)BINS) break;
             const uint32_t g = digit_base + hist[(size_t)d * nb + blockIdx.x];
+            if (BUCKET && blockIdx.x == 0) bucket_offs[d] = digit_base;
             if (REORDER) { gbase[d] = g; lstart[d] = local_base; }
             uint32_t r2 = REORDER ? local_base : g;
 #pragma unroll
@@ -302,7 +342,7 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
         for (int k = 0; k < ITEMS; k++) {
             const size_t i = wbase + (size_t)k * 64 + lane;
             if (i < n) {
-                const uint32_t d = (key[k] >> shift) & (BINS - 1);
+                const uint32_t d = digit_of(key[k]);
                 const uint32_t lp = cnt[w][d] + rank[k];
                 skey[lp] = key[k];
                 if constexpr (REORDER) sval[lp] = val[k];
@@ -357,7 +397,7 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
         for (int k = 0; k < ITEMS; k++) {
             const size_t i = wbase + (size_t)k * 64 + lane;
             if (i < n) {
-                const uint32_t d = (key[k] >> shift) & (BINS - 1);
+                const uint32_t d = digit_of(key[k]);
                 const uint32_t pos = cnt[w][d] + rank[k];
                 if constexpr (COUNTS) {
                     keys_out[pos] = pay[k];
@@ -708,6 +748,330 @@ bool small_sort_usable() {
     return state[dev].load(std::memory_order_acquire) > 0;
 }
 
+// =====================================================================================================
+// Depth sort by buckets, second half (common.h: depth sort by buckets): behind the bucket pass - histogram, row scan and stable
+// scatter on the bucket index, into the B side - every bucket is one contiguous run of (key, id) pairs in id order, and ONE launch
+// sorts them all, one workgroup per bucket, with the passes of small_sort_kernel (ballot ranking, wave-ordered LDS counters, three
+// barriers a pass, stable).  Inside a bucket the order of two keys is the order of the low s bits of key - kmin (the bits above
+// are the bucket index), so a workgroup sorts those, and of those only the ones in which its keys differ: two 8-bit passes where
+// the LSD sort of whole keys takes four.  The ids go to val_a and, in their place beside them in key_a, the tile counts
+// payload[id] - what the LSD sort's last scatter hands on (COUNTS).
+// The culled bucket (last bin) needs no sort - the stable scatter left it in id order - and is moved by DEPTH_BUCKET_COPY_GROUPS
+// workgroups of their own.  A bucket above DEPTH_BUCKET_CAP pairs (every Gaussian at one depth, say) owns the same index range on
+// both sides; its workgroup sorts it alone, in streaming LSD passes from one side to the other: slow, correct for any input, and
+// no workgroup ever waits for another.
+struct BucketSortLds {
+    uint32_t key[DEPTH_BUCKET_CAP];
+    uint32_t val[DEPTH_BUCKET_CAP];
+    uint32_t cnt[DEPTH_BUCKET_THREADS / 64][256];
+    uint32_t wsum[4];
+    uint32_t red[2][DEPTH_BUCKET_THREADS / 64];
+};
+static_assert(2 * sizeof(BucketSortLds) <= 160 * 1024, "two workgroups per CU");
+static_assert(DEPTH_BUCKET_CAP >= 512, "the streaming passes keep their digit offsets in the key image");
+
+// rank of an item among the items of its digit that the wave has seen so far in this pass (radix_scatter_kernel's ballot match)
+__device__ __forceinline__ uint32_t wave_digit_rank(uint32_t d, bool valid, volatile uint32_t* vcnt, unsigned long long lt_mask) {
+    const unsigned long long vm = __ballot(valid);
+    uint32_t p_lo = (uint32_t)vm, p_hi = (uint32_t)(vm >> 32);
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        const uint32_t x = 0u - ((d >> b) & 1u);
+        const unsigned long long nm = ~__ballot(x != 0u);
+        p_lo &= (uint32_t)nm ^ x;
+        p_hi &= (uint32_t)(nm >> 32) ^ x;
+    }
+    const unsigned long long peers = ((unsigned long long)p_hi << 32) | p_lo;
+    const uint32_t before = __popcll(peers & lt_mask);
+    const uint32_t old = vcnt[d];
+    if (valid && before == 0) vcnt[d] = old + (uint32_t)__popcll(peers);
+    return old + before;
+}
+
+// OR of v over the workgroup's threads (all of them call), in every thread; red: one word per wave
+__device__ __forceinline__ uint32_t bucket_block_or(uint32_t v, uint32_t* red) {
+    constexpr int NW = DEPTH_BUCKET_THREADS / 64;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 0; k < NW; k++) r |= red[k];
+    return r;
+}
+
+// A bucket above the capacity: streaming LSD passes B -> A -> B -> ... over its own index range, an odd number of them
+__device__ __forceinline__ void depth_bucket_stream_sort(BucketSortLds& L, uint32_t* key_b, uint32_t* val_b, uint32_t* key_a, uint32_t* val_a,
+                                                      uint32_t off, uint32_t n, uint32_t kmin, uint32_t low, uint32_t rel0,
+                                                      const uint32_t* __restrict__ payload) {
+    constexpr int THREADS = DEPTH_BUCKET_THREADS, ITEMS = 8, NW = THREADS / 64;       // (chunks of eight items a thread: fewer registers than the in-LDS path holds)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    volatile uint32_t* vcnt = &L.cnt[w][0];
+    uint32_t diff = 0;
+    for (uint32_t j = tid; j < n; j += THREADS) diff |= ((key_b[off + j] - kmin) & low) ^ rel0;
+    diff = bucket_block_or(diff, L.red[0]);
+    int passes = (32 - __clz((int)diff) + 7) / 8;
+    if ((passes & 1) == 0) passes++;          // (a pass on bits in which no two keys differ is a stable copy)
+    uint32_t* const gbase = L.key;            // [256] next position of every digit
+    uint32_t *sk = key_b, *sv = val_b, *dk = key_a, *dv = val_a;
+    for (int pass = 0; pass < passes; pass++) {
+        const int shift = 8 * pass;
+        const bool last = pass + 1 == passes;
+        auto digit_of = [&](uint32_t kk) -> uint32_t { return shift < 32 ? (((kk - kmin) & low) >> shift) & 255u : 0u; };
+        __syncthreads();
+        if (tid < 256) gbase[tid] = 0;
+        __syncthreads();
+        for (uint32_t j = tid; j < n; j += THREADS) atomicAdd(&gbase[digit_of(sk[off + j])], 1u);
+        __syncthreads();
+        {
+            const uint32_t tot = tid < 256 ? gbase[tid] : 0u;
+            uint32_t inc = tot;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t v = (uint32_t)__shfl_up((int)inc, d, 64);
+                if (lane >= d) inc += v;
+            }
+            if (tid < 256 && lane == 63) L.wsum[w] = inc;
+            __syncthreads();
+            if (tid < 256) {
+                uint32_t base = inc - tot;
+                for (int ww = 0; ww < w; ww++) base += L.wsum[ww];
+                gbase[tid] = base;
+            }
+        }
+        for (uint32_t c0 = 0; c0 < n; c0 += THREADS * ITEMS) {
+            // chunk of THREADS x ITEMS items in order: wave w owns 64 ITEMS consecutive ones
+            for (int d = tid; d < NW * 256; d += THREADS) (&L.cnt[0][0])[d] = 0;
+            __syncthreads();       // counters cleared, gbase final
+            const uint32_t wbase = c0 + (uint32_t)(w * ITEMS * 64 + lane);
+            uint32_t key[ITEMS], val[ITEMS], rank[ITEMS];
+#pragma unroll
+            for (int k = 0; k < ITEMS; k++) {
+                const uint32_t i = wbase + (uint32_t)(k * 64);
+                const uint32_t ii = off + (i < n ? i : 0u);
+                key[k] = sk[ii];
+                val[k] = sv[ii];
+            }
+#pragma unroll
+            for (int k = 0; k < ITEMS; k++) {
+                const uint32_t i = wbase + (uint32_t)(k * 64);
+                rank[k] = wave_digit_rank(digit_of(key[k]), i < n, vcnt, lt_mask);
+            }
+            __syncthreads();
+            if (tid < 256) {
+                uint32_t base = gbase[tid];
+#pragma unroll
+                for (int ww = 0; ww < NW; ww++) {
+                    const uint32_t c = L.cnt[ww][tid];
+                    L.cnt[ww][tid] = base;
+                    base += c;
+                }
+                gbase[tid] = base;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < ITEMS; k++) {
+                const uint32_t i = wbase + (uint32_t)(k * 64);
+                if (i < n) {
+                    const uint32_t pos = off + L.cnt[w][digit_of(key[k])] + rank[k];
+                    dk[pos] = last ? payload[val[k]] : key[k];
+                    dv[pos] = val[k];
+                }
+            }
+            __syncthreads();       // every offset read before the next chunk clears the counters
+        }
+        // this pass's stores are read by the next one - by other waves of this workgroup: written back in front of the barrier, the
+        // CU's cache dropped behind it
+        __threadfence();
+        __syncthreads();
+        __threadfence();
+        uint32_t* t = sk; sk = dk; dk = t;
+        t = sv; sv = dv; dv = t;
+    }
+}
+
+// (the four arrays are read AND written by the streaming passes: no __restrict__, no const)
+__global__ void __launch_bounds__(DEPTH_BUCKET_THREADS, 4)      // (four waves per SIMD: two workgroups per CU)
+depth_bucket_sort_kernel(uint32_t* key_b, uint32_t* val_b, uint32_t* key_a, uint32_t* val_a, uint32_t bins,
+                         const uint32_t* __restrict__ totals, const uint32_t* __restrict__ offs, uint32_t* __restrict__ ctl,
+                         const uint32_t* __restrict__ payload, uint32_t* __restrict__ stats_host) {
+    extern __shared__ __attribute__((aligned(16))) char bucket_sort_smem[];
+    BucketSortLds& L = *reinterpret_cast<BucketSortLds*>(bucket_sort_smem);
+    constexpr int THREADS = DEPTH_BUCKET_THREADS, ITEMS = DEPTH_BUCKET_ITEMS, NW = THREADS / 64;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t b = blockIdx.x;
+    if (b >= bins - 1u) {
+        // the culled bucket: ids in id order already, moved to the A side with their tile counts
+        const uint32_t off = offs[bins - 1u], n = totals[bins - 1u];
+        for (uint32_t j = (b - (bins - 1u)) * THREADS + tid; j < n; j += DEPTH_BUCKET_COPY_GROUPS * THREADS) {
+            const uint32_t id = val_b[off + j];
+            val_a[off + j] = id;
+            key_a[off + j] = payload[id];
+        }
+        if (b == bins - 1u) {
+            // the frame's largest sorted bucket and how many are above the capacity (f3dgs_depth_sort_info)
+            uint32_t mx = 0, over = 0;
+            for (uint32_t d = tid; d < bins - 1u; d += THREADS) {
+                const uint32_t t = totals[d];
+                mx = max(mx, t);
+                over += t > (uint32_t)DEPTH_BUCKET_CAP ? 1u : 0u;
+            }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+                over += (uint32_t)__shfl_xor((int)over, d, 64);
+            }
+            if (lane == 0) { L.red[0][w] = mx; L.red[1][w] = over; }
+            __syncthreads();
+            if (tid == 0) {
+                mx = 0; over = 0;
+                for (int k = 0; k < NW; k++) { mx = max(mx, L.red[0][k]); over += L.red[1][k]; }
+                ctl[2] = mx; ctl[3] = over;
+                if (stats_host) {
+                    __hip_atomic_store(&stats_host[0], mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(&stats_host[1], over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __threadfence_system();
+                }
+            }
+        }
+        return;
+    }
+    const uint32_t n = totals[b];
+    if (n == 0) return;
+    const uint32_t off = offs[b];
+    const uint32_t kmin = ctl[0], bshift = ctl[1];
+    const uint32_t low = (1u << bshift) - 1u;             // (the shift is 29 at most: depth_bucket_shift)
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const uint32_t rel0 = (key_b[off] - kmin) & low;
+    volatile uint32_t* vcnt = &L.cnt[w][0];
+
+    if (n <= (uint32_t)DEPTH_BUCKET_CAP) {
+        // item order: wave w owns [64 steps w, 64 steps (w + 1)), visited in `steps` steps of 64 consecutive items
+        const int steps = (int)((n + THREADS - 1) / THREADS);
+        const uint32_t wbase = (uint32_t)(w * steps * 64 + lane);
+        uint32_t key[ITEMS], val[ITEMS], rank[ITEMS];
+        uint32_t diff = 0;
+#pragma unroll
+        for (int k = 0; k < ITEMS; k++) {
+            const uint32_t i = wbase + (uint32_t)(k * 64);
+            const bool mine = k < steps && i < n;
+            const uint32_t ii = mine ? off + i : off;         // (unconditional: one run of requests)
+            const uint32_t kk = key_b[ii];
+            val[k] = val_b[ii];
+            key[k] = mine ? (kk - kmin) & low : rel0;
+            diff |= key[k] ^ rel0;
+        }
+        diff = bucket_block_or(diff, L.red[0]);
+        const int passes = (32 - __clz((int)diff) + 7) / 8;       // (diff == 0: __clz gives 32, no pass)
+        if (passes == 0) {
+            // one key throughout: the bucket is in order as it stands
+#pragma unroll
+            for (int k = 0; k < ITEMS; k++) {
+                const uint32_t i = wbase + (uint32_t)(k * 64);
+                if (k < steps && i < n) {
+                    val_a[off + i] = val[k];
+                    key_a[off + i] = payload[val[k]];
+                }
+            }
+            return;
+        }
+        for (int pass = 0; pass < passes; pass++) {
+            const int shift = 8 * pass;
+            for (int d = tid; d < NW * 256; d += THREADS) (&L.cnt[0][0])[d] = 0;
+            __syncthreads();       // counters cleared; the previous pass's read-back is complete
+#pragma unroll
+            for (int k = 0; k < ITEMS; k++) {
+                if (k >= steps) break;
+                const uint32_t i = wbase + (uint32_t)(k * 64);
+                rank[k] = wave_digit_rank((key[k] >> shift) & 255u, i < n, vcnt, lt_mask);
+            }
+            __syncthreads();
+            {
+                uint32_t tot = 0;
+                if (tid < 256) {
+#pragma unroll
+                    for (int ww = 0; ww < NW; ww++) tot += L.cnt[ww][tid];
+                }
+                uint32_t inc = tot;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t v = (uint32_t)__shfl_up((int)inc, d, 64);
+                    if (lane >= d) inc += v;
+                }
+                if (tid < 256 && lane == 63) L.wsum[w] = inc;
+                __syncthreads();
+                if (tid < 256) {
+                    uint32_t base = inc - tot;
+                    for (int ww = 0; ww < w; ww++) base += L.wsum[ww];
+#pragma unroll
+                    for (int ww = 0; ww < NW; ww++) {
+                        const uint32_t c = L.cnt[ww][tid];
+                        L.cnt[ww][tid] = base;
+                        base += c;
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < ITEMS; k++) {
+                const uint32_t i = wbase + (uint32_t)(k * 64);
+                if (k < steps && i < n) {
+                    const uint32_t pos = L.cnt[w][(key[k] >> shift) & 255u] + rank[k];
+                    L.key[pos] = key[k];
+                    L.val[pos] = val[k];
+                }
+            }
+            __syncthreads();
+            if (pass + 1 < passes) {
+#pragma unroll
+                for (int k = 0; k < ITEMS; k++) {
+                    const uint32_t i = wbase + (uint32_t)(k * 64);
+                    if (k < steps && i < n) { key[k] = L.key[i]; val[k] = L.val[i]; }
+                }
+            }
+        }
+        // out in the new order, eight items of a thread at a time: their gathers all go out before the first store
+        constexpr int HALF = ITEMS / 2;
+        for (int h = 0; h < 2; h++) {
+            if ((uint32_t)(h * HALF * THREADS) >= n) break;
+            uint32_t id[HALF], c[HALF];
+#pragma unroll
+            for (int k = 0; k < HALF; k++) {
+                const uint32_t j = (uint32_t)((h * HALF + k) * THREADS + tid);
+                id[k] = L.val[j < n ? j : 0u];
+                c[k] = payload[id[k]];
+            }
+#pragma unroll
+            for (int k = 0; k < HALF; k++) {
+                const uint32_t j = (uint32_t)((h * HALF + k) * THREADS + tid);
+                if (j < n) {
+                    val_a[off + j] = id[k];
+                    key_a[off + j] = c[k];
+                }
+            }
+        }
+        return;
+    }
+
+    depth_bucket_stream_sort(L, key_b, val_b, key_a, val_a, off, n, kmin, low, rel0, payload);
+}
+
+bool depth_bucket_sort_usable() {
+    constexpr int MAX_DEV = 64;
+    static std::atomic<int> state[MAX_DEV];      // 0: not asked yet, 1: usable, -1: refused
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return false;
+    if (state[dev].load(std::memory_order_acquire) == 0) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&depth_bucket_sort_kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BucketSortLds));
+        if (e != hipSuccess) (void)hipGetLastError();
+        state[dev].store(e == hipSuccess ? 1 : -1, std::memory_order_release);
+    }
+    return state[dev].load(std::memory_order_acquire) > 0;
+}
+
 // ITEMS = keys per thread: 8 for the depth sort (2048-key workgroups: P = 1M gives 489 workgroups, about two per CU;
 // with 16 there are fewer workgroups than CUs and every pass is one latency chain: 0.116 -> 0.097 ms at c3), 16 for
 // the tile sort (twice the instances, and the LDS reorder pays more on longer runs: 0.119 vs 0.128 ms with 8).
@@ -722,23 +1086,25 @@ static hipError_t radix_pass(const uint32_t* ki, const uint32_t* vi, uint32_t* k
     const uint32_t nb = (uint32_t)((n + SORT_THREADS * ITEMS - 1) / (SORT_THREADS * ITEMS));
     uint32_t* totals = hist + (size_t)BINS * nb;
     hipLaunchKernelGGL((radix_hist_kernel<BITS, ITEMS>), dim3(nb), dim3(SORT_THREADS), 0, s, ki, n, shift, nb, hist,
-                       tj ? *tj : TotalsJob{nullptr, 0, nullptr, nullptr}, n_dev);
+                       tj ? *tj : TotalsJob{nullptr, 0, nullptr, nullptr}, n_dev, 0u, (uint32_t*)nullptr);
     if (tj && tj->ready) rc = hipEventRecord(tj->ready, s);        // the totals are final behind this launch
     hipLaunchKernelGGL(radix_rowscan_kernel, dim3(BINS), dim3(256), 0, s, hist, nb, totals);
     const uint32_t* const no_payload = nullptr;
+    const uint32_t* const no_ctl = nullptr;
+    uint32_t* const no_offs = nullptr;
     if constexpr (ITEMS == SORT_ITEMS && (BITS == RADIX_BITS || BITS == DEPTH_RADIX_BITS)) {        // the depth sort's shapes
         if (payload) {
             hipLaunchKernelGGL((radix_scatter_kernel<BITS, ITEMS, (BITS <= 8), false, true>), dim3(nb), dim3(SORT_THREADS), 0, s, ki,
-                               vi, ko, vo, n, shift, nb, hist, totals, (uint2*)nullptr, n_dev, payload);
+                               vi, ko, vo, n, shift, nb, hist, totals, (uint2*)nullptr, n_dev, payload, no_ctl, no_offs);
             return rc;
         }
     }
     if (ranges_enc && BITS <= 8)
         hipLaunchKernelGGL((radix_scatter_kernel<BITS, ITEMS, true, true>), dim3(nb), dim3(SORT_THREADS), 0, s, ki, vi, ko, vo, n,
-                           shift, nb, hist, totals, ranges_enc, n_dev, no_payload);
+                           shift, nb, hist, totals, ranges_enc, n_dev, no_payload, no_ctl, no_offs);
     else
         hipLaunchKernelGGL((radix_scatter_kernel<BITS, ITEMS, (BITS <= 8), false>), dim3(nb), dim3(SORT_THREADS), 0, s, ki, vi, ko,
-                           vo, n, shift, nb, hist, totals, (uint2*)nullptr, n_dev, no_payload);
+                           vo, n, shift, nb, hist, totals, (uint2*)nullptr, n_dev, no_payload, no_ctl, no_offs);
     return rc;
 }
 
@@ -790,14 +1156,16 @@ void launch_radix_sort_pairs(uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, 
     }
 }
 
-// Depth sort of the Gaussians: 32-bit keys in `keys` (read-only), values = indices.  Three passes of 11/11/10
-// bits; the sorted ids end in val_a, and in key_a the sorted keys - or, given `counts_in_a`, what the frame reads next in that
-// order: the tile counts (common.h).
+// Depth sort of the Gaussians: 32-bit keys in `keys` (read-only), values = indices.  Up to SMALL_SORT_MAX keys: one launch; beyond,
+// with `buckets`: one bucket pass and one launch that sorts the buckets (four launches); else three passes of 11/11/10 bits or,
+// above 200,000 keys, four of 8.  The sorted ids end in val_a, and in key_a the sorted keys - or, given `counts_in_a`, what the
+// frame reads next in that order: the tile counts (common.h).
 hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, uint32_t* val_b, size_t n,
                              uint32_t* hist, const TotalsJob* tj, hipStream_t s, const OffsetSumsJob* sums, bool* sums_done,
-                             bool* counts_in_a) {
+                             bool* counts_in_a, bool buckets, uint32_t* stats_host, DepthSortInfo* info) {
     if (sums_done) *sums_done = false;
     if (counts_in_a) *counts_in_a = false;
+    if (info) *info = DepthSortInfo{F3DGS_DEPTH_SORT_NONE, 0u, 0u};
     if (n == 0) return hipSuccess;
     if (n <= (size_t)SMALL_SORT_MAX && small_sort_usable<false>()) {
         // the totals the host waits for go out in a launch of their own, in FRONT of the sort: behind it the host would sit out the
@@ -814,10 +1182,47 @@ hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* va
                            key_a, val_a, (uint32_t)n, 4, (tj && tj->partial && !apart) ? *tj : TotalsJob{nullptr, 0, nullptr, nullptr},
                            (uint2*)nullptr, (const uint32_t*)nullptr, sums ? *sums : OffsetSumsJob{nullptr, nullptr, nullptr});
         if (sums && sums_done) *sums_done = true;
+        if (info) info->path = F3DGS_DEPTH_SORT_ONE_LAUNCH;
         return rc;
     }
     // the last pass hands the tile counts on in the new order instead of the keys, where the caller can take them
     const uint32_t* const payload = (counts_in_a && sums) ? sums->tiles_touched : nullptr;
+    if (buckets && payload && tj && tj->partial && n < (1ull << 31) && depth_bucket_sort_usable()) {
+        // four launches: the bucket pass into the B side (histogram - with the totals job and the key range -, row scan, stable
+        // scatter), then every bucket sorted inside LDS into the A side (depth_bucket_sort_kernel)
+        const uint32_t count = depth_bucket_count(n);
+        const uint32_t nb = (uint32_t)((n + SORT_THREADS * SORT_ITEMS - 1) / (SORT_THREADS * SORT_ITEMS));
+        const bool wide = depth_bucket_bits(n) == DEPTH_BUCKET_BITS_WIDE;
+        const uint32_t bins = 1u << depth_bucket_bits(n);
+        uint32_t* const totals = hist + (size_t)bins * nb;
+        uint32_t* const offs = totals + bins;
+        uint32_t* const ctl = offs + bins;
+        const uint32_t* const none = nullptr;
+        if (wide)
+            hipLaunchKernelGGL((radix_hist_kernel<DEPTH_BUCKET_BITS_WIDE, SORT_ITEMS, true>), dim3(nb), dim3(SORT_THREADS), 0, s, keys, n, 0,
+                               nb, hist, *tj, none, count, ctl);
+        else
+            hipLaunchKernelGGL((radix_hist_kernel<DEPTH_BUCKET_BITS, SORT_ITEMS, true>), dim3(nb), dim3(SORT_THREADS), 0, s, keys, n, 0,
+                               nb, hist, *tj, none, count, ctl);
+        hipError_t rc = hipSuccess;
+        if (tj->ready) rc = hipEventRecord(tj->ready, s);        // the totals are final behind this launch
+        hipLaunchKernelGGL(radix_rowscan_kernel, dim3(bins), dim3(256), 0, s, hist, nb, totals);
+        if (wide)
+            hipLaunchKernelGGL((radix_scatter_kernel<DEPTH_BUCKET_BITS_WIDE, SORT_ITEMS, false, false, false, true>), dim3(nb),
+                               dim3(SORT_THREADS), 0, s, keys, none, key_b, val_b, n, 0, nb, hist, totals, (uint2*)nullptr, none, none,
+                               (const uint32_t*)ctl, offs);
+        else
+            hipLaunchKernelGGL((radix_scatter_kernel<DEPTH_BUCKET_BITS, SORT_ITEMS, false, false, false, true>), dim3(nb),
+                               dim3(SORT_THREADS), 0, s, keys, none, key_b, val_b, n, 0, nb, hist, totals, (uint2*)nullptr, none, none,
+                               (const uint32_t*)ctl, offs);
+        hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(bins - 1u + DEPTH_BUCKET_COPY_GROUPS), dim3(DEPTH_BUCKET_THREADS),
+                           sizeof(BucketSortLds), s, key_b, val_b, key_a, val_a, bins, (const uint32_t*)totals, (const uint32_t*)offs, ctl,
+                           payload, stats_host);
+        *counts_in_a = true;
+        if (info) *info = DepthSortInfo{F3DGS_DEPTH_SORT_BUCKETS, count, (uint32_t)DEPTH_BUCKET_CAP};
+        return rc;
+    }
+    if (info) info->path = F3DGS_DEPTH_SORT_PASSES;
     if (n > 200000) {
         // large P: four 8-bit passes are faster than three 11-bit ones (measured at 1M: 0.105 vs 0.148 ms);
         // small P is launch-bound and prefers fewer passes.  Result must end in (key_a, val_a): A <- keys, then

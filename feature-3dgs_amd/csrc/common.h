@@ -98,6 +98,62 @@ static_assert(tile_digit_split(15).width[0] == 8 && tile_digit_split(15).width[1
 static_assert(tile_digit_split(16).width[0] == 8 && tile_digit_split(16).width[1] == 8, "16 = 8 + 8");
 static_assert(tile_digit_split(8).passes == 1 && tile_digit_split(8).width[0] == 8 && tile_digit_split(5).width[0] == 5, "one pass: the bits themselves");
 
+// ---- depth sort by buckets (binning.hip: launch_depth_sort) -----------------------------------------------------------------
+// One stable most-significant pass cuts the depth keys into buckets, ONE launch then sorts every bucket inside LDS.  The bucket of
+// a key is a monotone integer function of its bits, b = (key - kmin) >> s, with kmin / kmax the frame's smallest and largest
+// alive key (float bits: a logarithmic scale, so one far outlier costs one octave's share of the buckets per octave and not the
+// whole resolution, as it would on a scale linear in z).  The pass ranks DEPTH_BUCKET_BITS or DEPTH_BUCKET_BITS_WIDE bits; of
+// its 2^bits bins the last one holds the culled Gaussians (key all-ones), which need no sort, and `count - 1` of the others are
+// in use, `count` chosen from P so that a mean bucket is about an eighth of the capacity.
+constexpr int DEPTH_BUCKET_BITS = 10;                 // P up to DEPTH_BUCKET_WIDE_ABOVE
+constexpr int DEPTH_BUCKET_BITS_WIDE = 11;            // beyond
+constexpr size_t DEPTH_BUCKET_WIDE_ABOVE = 1250000;
+constexpr int DEPTH_BUCKET_THREADS = 512;
+constexpr int DEPTH_BUCKET_ITEMS = 16;
+// pairs a bucket may hold to be sorted inside LDS (two workgroups of 8 bytes a pair and 8 KB of counters share a CU's 160 KB);
+// a larger one is sorted by its workgroup alone in streaming passes between the two ping-pong buffers
+constexpr int DEPTH_BUCKET_CAP = 8064;
+constexpr int DEPTH_BUCKET_MEAN = 1024;               // Gaussians per bucket the count aims at
+constexpr int DEPTH_BUCKET_MIN_COUNT = 16;
+constexpr int DEPTH_BUCKET_COPY_GROUPS = 128;         // workgroups that move the culled bucket (no sort: the stable pass left it in id order)
+// option depth_sort_buckets = -1: the bucket path is taken for DEPTH_BUCKET_AUTO_ABOVE < P <= DEPTH_BUCKET_AUTO_UPTO, where it was
+// measured faster than the multi-launch LSD passes (profiles/depth_bucket_sort.md): from the first size beyond the one-launch sort
+// (16,385: 0.038 against 0.065 ms) to the last size of the 10-bit pass (1.25M: 0.092 against 0.108); the 11-bit pass loses at 2M
+// (0.146 against 0.142), and at 5M the buckets of an even spread no longer fit the capacity
+constexpr size_t DEPTH_BUCKET_AUTO_ABOVE = SMALL_SORT_MAX;
+constexpr size_t DEPTH_BUCKET_AUTO_UPTO = DEPTH_BUCKET_WIDE_ABOVE;
+static_assert(DEPTH_BUCKET_CAP <= DEPTH_BUCKET_THREADS * DEPTH_BUCKET_ITEMS && DEPTH_BUCKET_CAP % 64 == 0, "a bucket in LDS: whole waves, within the threads' items");
+static_assert(2 * (2 * 4 * DEPTH_BUCKET_CAP + 4 * 256 * (DEPTH_BUCKET_THREADS / 64) + 64) <= 160 * 1024, "two workgroups per CU");
+
+constexpr int depth_bucket_bits(size_t P) { return P > DEPTH_BUCKET_WIDE_ABOVE ? DEPTH_BUCKET_BITS_WIDE : DEPTH_BUCKET_BITS; }
+// bins of the pass in use (a power of two, the culled bin included): the smallest that keeps the mean bucket at DEPTH_BUCKET_MEAN
+constexpr uint32_t depth_bucket_count(size_t P) {
+    const uint32_t most = 1u << depth_bucket_bits(P);
+    uint32_t c = DEPTH_BUCKET_MIN_COUNT;
+    while (c < most && (size_t)c * DEPTH_BUCKET_MEAN < P) c <<= 1;
+    return c;
+}
+// smallest shift that maps [kmin, kmax] onto buckets 0 .. count - 2; an empty or one-key range (kmax <= kmin) gives 0
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr uint32_t depth_bucket_shift(uint32_t kmin, uint32_t kmax, uint32_t count) {
+    const uint32_t range = kmax > kmin ? kmax - kmin : 0u;
+    uint32_t s = 0;
+    while ((range >> s) > count - 2u) s++;
+    return s;
+}
+static_assert(depth_bucket_count(16385) == 32 && depth_bucket_count(16384) == 16 && depth_bucket_count(1) == 16, "mean bucket <= 1024, sixteen bins at least");
+static_assert(depth_bucket_count(1000000) == 1024 && depth_bucket_count(1250000) == 1024 && depth_bucket_count(1250001) == 2048 &&
+              depth_bucket_count(5000000) == 2048, "as many bins as the pass ranks bits, no more");
+static_assert(depth_bucket_shift(5, 5, 16) == 0 && depth_bucket_shift(0xFFFFFFFFu, 0u, 16) == 0, "one key or none: no shift, bucket 0");
+static_assert(depth_bucket_shift(0, 14, 16) == 0 && depth_bucket_shift(0, 15, 16) == 1, "the last bucket in use is count - 2");
+static_assert(depth_bucket_shift(0x40000000u, 0x41200000u, 1024) == 15, "z in 2 .. 10 over 1024 bins: 576 buckets of 2^15 keys");
+static_assert(depth_bucket_shift(0u, 0xFFFFFFFEu, 16) == 29 && (0xFFFFFFFEu >> 29) <= 14u, "the widest range stays below 32");
+
+constexpr int DEPTH_BUCKET_CTL_WORDS = 64;            // [0] kmin, [1] shift, [2] largest bucket, [3] buckets above the capacity
+static_assert(DEPTH_BUCKET_BITS_WIDE <= DEPTH_RADIX_BITS, "GeomState::hist is sized for the widest depth pass");
+
 inline size_t sort_blocks(size_t n) { return (n + SORT_CHUNK - 1) / SORT_CHUNK; }
 inline size_t scan_blocks(size_t n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK; }
 inline size_t depth_sort_blocks(size_t n) { return (n + SORT_THREADS * DEPTH_SORT_ITEMS - 1) / (SORT_THREADS * DEPTH_SORT_ITEMS); }
@@ -115,10 +171,12 @@ struct GeomState {
     uint32_t* key_b;
     uint32_t* val_a;
     uint32_t* val_b;
-    uint32_t* hist;           // RADIX_BINS * sort_blocks(P) + RADIX_BINS
+    uint32_t* hist;           // DEPTH_RADIX_BINS * sort_blocks(P) + DEPTH_RADIX_BINS (histogram matrix and totals of a pass), and behind
+                              //     them, for the bucket pass, the buckets' offsets and DEPTH_BUCKET_CTL_WORDS control words
     uint32_t* scan_tmp;       // scan_blocks(P) + 8      list entries of every chunk of SCAN_CHUNK Gaussians in depth order
     uint32_t* scan_sub;       // 64 x scan_blocks(P)     list entries of every run of 64 Gaussians in depth order
-    uint32_t* ref_partial;    // per preprocess workgroup: bounding-rectangle tile counts, then list-entry counts, then 1 if a visible Gaussian of the workgroup has a long axis
+    uint32_t* ref_partial;    // per preprocess workgroup: bounding-rectangle tile counts, then list-entry counts, then 1 if a visible Gaussian of the workgroup has a long axis,
+                              //     then the smallest and the largest depth key of its alive Gaussians (all-ones / zero: none)
     uint32_t* counters;       // 16 words: [0] = instances in the (culled) lists, [1] = reference num_rendered, [2] != 0: a visible Gaussian has a long axis, [3] = entries the binning buffer was carved for (0 until the emit kernel ran)
     // -- control words of the single-pass sorts (lookback.h).  depth_hist is zeroed by preprocess_kernel (it is
     //    accumulated by the kernel after it); everything from lb_words on is zeroed by sort_prologue_kernel.
@@ -145,10 +203,10 @@ struct GeomState {
         g.key_b = c.take<uint32_t>(P);
         g.val_a = c.take<uint32_t>(P);
         g.val_b = c.take<uint32_t>(P);
-        g.hist = c.take<uint32_t>(DEPTH_RADIX_BINS * sort_blocks(P) + DEPTH_RADIX_BINS);
+        g.hist = c.take<uint32_t>(DEPTH_RADIX_BINS * sort_blocks(P) + 2 * DEPTH_RADIX_BINS + DEPTH_BUCKET_CTL_WORDS);
         g.scan_tmp = c.take<uint32_t>(scan_blocks(P) + 8);
         g.scan_sub = c.take<uint32_t>(64 * scan_blocks(P));
-        g.ref_partial = c.take<uint32_t>(3 * ((P + 255) / 256) + 3);
+        g.ref_partial = c.take<uint32_t>(5 * ((P + 255) / 256) + 5);
         g.counters = c.take<uint32_t>(16);
         g.depth_hist = c.take<uint32_t>(4 * 256);
         g.big_ctl = c.take<uint32_t>(4 + BIGQ_CAP);
@@ -230,6 +288,7 @@ struct Options {
     int bwd_pl;          // blend backward: pixel-lane formulation with all sums on the matrix pipe: 1 always, 0 never, -1 (default) for C > 0 (C > 4 with bwd_bf16 = 0); needs feature_mfma
     int fwd_wide;        // blend forward: 128-channel windows where more than 64 channels remain (default 1)
     int fwd_solo;        // blend forward, one quadrant per wave: one 64-thread workgroup per quadrant (default 1; the waves never synchronise)
+    int depth_sort_buckets;   // depth sort of more than SMALL_SORT_MAX Gaussians: one bucket pass and an in-LDS sort per bucket instead of the LSD passes: 1 always, 0 never, -1 (default) for DEPTH_BUCKET_AUTO_ABOVE < P <= DEPTH_BUCKET_AUTO_UPTO
     int sort_onesweep;   // 1: single-pass radix passes with decoupled look-back (measured slower on MI355X; default 0)
     int sync_free;       // -1 (default): as 1 inside a graph capture, as 0 otherwise; 1: the forward call never waits for the instance count in the middle of its enqueue - binning buffers of a CAPACITY, kernels that read the count on the device, the count checked behind the last launch (one retry) - and can be captured in a HIP graph; 0: the blocking read, capture refused
     int instance_capacity;   // sync_free: entries of the instance lists to provide for (0, default: 1.25 x the thread's last count on the device + 4096)
@@ -316,9 +375,19 @@ struct TotalsJob {
 // `sums` (optional) / `sums_done`: see OffsetSumsJob - *sums_done says whether this call produced them
 // `counts_in_a` (optional, needs `sums`): the multi-launch sort's last pass stores sums->tiles_touched[id] at every id's place in
 // the order - into key_a, instead of the sorted keys - and sets *counts_in_a; the one-workgroup sort (sums_done) does not
+// `buckets` (needs tj, sums and counts_in_a): take the bucket path where n > SMALL_SORT_MAX (common.h: depth sort by buckets);
+// `stats_host` (optional, pinned and device-visible): receives the largest bucket and the number of buckets above the capacity;
+// `info` (optional): what was launched
+struct DepthSortInfo {
+    int path;                  // F3DGS_DEPTH_SORT_* (f3dgs.h)
+    uint32_t buckets;          // bins of the bucket pass in use, the culled one included (0: another path)
+    uint32_t capacity;         // pairs a bucket may hold to be sorted inside LDS
+};
 hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, uint32_t* val_b, size_t n,
                              uint32_t* hist, const TotalsJob* tj, hipStream_t s, const OffsetSumsJob* sums = nullptr,
-                             bool* sums_done = nullptr, bool* counts_in_a = nullptr);
+                             bool* sums_done = nullptr, bool* counts_in_a = nullptr, bool buckets = false,
+                             uint32_t* stats_host = nullptr, DepthSortInfo* info = nullptr);
+bool depth_bucket_sort_usable();       // the bucket sort's LDS image is above the default limit: raised once per device
 void launch_iota(uint32_t* dst, size_t n, hipStream_t s);
 void launch_radix_sort_keys_to_order(const uint32_t* keys, uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, uint32_t* val_b,
                                      size_t n, int nbits, uint32_t* hist, hipStream_t s);

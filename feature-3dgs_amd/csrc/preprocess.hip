@@ -439,15 +439,23 @@ preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, const 
     // pinned words.  The same goes for the length of our own (culled) instance lists: both totals are known right
     // after this kernel, long before the host needs them (it waits for them while the depth sort runs).
     // Third partial: does the workgroup hold a visible Gaussian with a long axis (one ballot per wave).
-    __shared__ uint32_t wsum[3][4];
+    // Fourth and fifth: the smallest and the largest depth key of the workgroup's alive Gaussians (all-ones / zero where it has
+    // none) - the bucket pass of the depth sort spreads its buckets over that range (common.h: depth_bucket_shift).
+    __shared__ uint32_t wsum[5][4];
     uint32_t v = bbox_tiles, u = out_tiles;
+    uint32_t kmn = out_key, kmx = out_key == 0xFFFFFFFFu ? 0u : out_key;
     const uint32_t ar = __ballot(alive && long_axis) != 0ull ? 1u : 0u;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         v += (uint32_t)__shfl_xor((int)v, d, 64);
         u += (uint32_t)__shfl_xor((int)u, d, 64);
+        kmn = min(kmn, (uint32_t)__shfl_xor((int)kmn, d, 64));
+        kmx = max(kmx, (uint32_t)__shfl_xor((int)kmx, d, 64));
     }
-    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = v; wsum[1][threadIdx.x >> 6] = u; wsum[2][threadIdx.x >> 6] = ar; }
+    if ((threadIdx.x & 63) == 0) {
+        wsum[0][threadIdx.x >> 6] = v; wsum[1][threadIdx.x >> 6] = u; wsum[2][threadIdx.x >> 6] = ar;
+        wsum[3][threadIdx.x >> 6] = kmn; wsum[4][threadIdx.x >> 6] = kmx;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         const int nbp = (P + 255) / 256;      // padding workgroups (tiny P) have nothing to report
@@ -455,6 +463,8 @@ preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, const 
             ref_partial[blockIdx.x] = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3];
             ref_partial[nbp + blockIdx.x] = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
             ref_partial[2 * nbp + blockIdx.x] = max(max(wsum[2][0], wsum[2][1]), max(wsum[2][2], wsum[2][3]));
+            ref_partial[3 * nbp + blockIdx.x] = min(min(wsum[3][0], wsum[3][1]), min(wsum[3][2], wsum[3][3]));
+            ref_partial[4 * nbp + blockIdx.x] = max(max(wsum[4][0], wsum[4][1]), max(wsum[4][2], wsum[4][3]));
         }
     }
 }

@@ -88,6 +88,13 @@ const char* f3dgs_last_error(void);
  *   "profile"        1: per-stage HIP events, see f3dgs_profile_read; 2: only around the two blend kernels
  *   "sort_onesweep"  0 (default): three-kernel radix passes; 1: single-pass radix scatter with decoupled look-back
  *                    (measured slower on MI355X, kept as a tested alternative)
+ *   "depth_sort_buckets"  depth sort of more than 16,384 Gaussians: ONE stable pass that cuts the depth keys into up to 2,047
+ *                    buckets by (key - smallest alive key) >> shift, then one launch that sorts every bucket inside LDS (four
+ *                    launches, two trips through memory) instead of three or four LSD passes (nine or twelve launches): 1 always,
+ *                    0 never, -1 (default) for 16,384 < P <= 1,250,000, where it was measured faster.  The lists are the same
+ *                    bits either way, for any input: a bucket of more than 8,064 Gaussians (many at one depth) is sorted by
+ *                    its workgroup alone in streaming passes - correct, slow; f3dgs_depth_sort_info counts them.  Environment:
+ *                    F3DGS_DEPTH_SORT_BUCKETS.  Not with sort_onesweep = 1.
  *   "bwd_pl"         blend backward formulation: 1 pixel-lane kernel (all sums on the matrix pipe), 0 instance-lane
  *                    kernel, -1 (default) by channel count (pixel-lane from the first feature channel on; from five with
  *                    bwd_bf16 = 0)
@@ -158,6 +165,17 @@ int f3dgs_last_backward_contraction(void);
  * [4] sticky - an emit wave of a CAPTURED frame found no room (the caller clears it).  They are final once the frame's work has
  * completed (synchronise first); a replayed graph writes the words of the call it was captured from. */
 const uint32_t* f3dgs_forward_counts(void);
+/* How the calling thread's most recent f3dgs_forward call sorted its Gaussians by depth (read-only; NULL before the first call):
+ * [0] the path, F3DGS_DEPTH_SORT_*, [1] bins of the bucket pass in use, the one of the culled Gaussians included, [2] Gaussians a
+ * bucket may hold to be sorted inside LDS, [3] the frame's largest bucket, [4] its buckets above [2] ([1 .. 4]: zero on the other
+ * paths).  [3] and [4] are written by the frame's kernels: final once its work has completed (synchronise first).  The pointer
+ * is good until this thread's next call of this function. */
+#define F3DGS_DEPTH_SORT_NONE 0        /* P = 0 */
+#define F3DGS_DEPTH_SORT_ONE_LAUNCH 1  /* up to 16,384 Gaussians: one workgroup */
+#define F3DGS_DEPTH_SORT_PASSES 2      /* LSD passes of three launches each */
+#define F3DGS_DEPTH_SORT_BUCKETS 3     /* option depth_sort_buckets */
+#define F3DGS_DEPTH_SORT_LOOKBACK 4    /* option sort_onesweep */
+const uint32_t* f3dgs_depth_sort_info(void);
 /* ONE view split over several GPUs by tile rows (no counterpart in the reference; SURVEY.md 8(e), "alternative for single huge
  * views"): from this call on the f3dgs_forward calls of this THREAD list and blend only the tiles of rows [tile_row_begin,
  * tile_row_end) of the 16 x 16 tile grid (clipped to the grid; (0, 0) restores the whole view; any other pair with begin >= end
