@@ -1254,6 +1254,7 @@ int f3dgs_debug_read(const char* what, int P, int C, int R, int width, int heigh
     else if (w == "tiles_touched") { src = geom.tiles_touched; bytes = (size_t)P * 4; }
     else if (w == "depth_key") { src = geom.depth_key; bytes = (size_t)P * 4; }
     else if (w == "order") { src = geom.val_a; bytes = (size_t)P * 4; }
+    else if (w == "order_counts") { src = geom.key_a; bytes = (size_t)P * 4; }
     else if (w == "counters") { src = geom.counters; bytes = 16 * 4; }
     else if (w == "point_list") { src = bin.point_list; bytes = (size_t)n_list * 4; }
     else if (w == "tile_sorted") { src = bin.tile_sorted; bytes = (size_t)n_list * 4; }

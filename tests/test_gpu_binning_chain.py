@@ -6,15 +6,18 @@ by tile id in digits as wide as the tile count needs (binning.hip).  Every case 
 element for element and without a tolerance, as test_gpu_parity.test_binning_is_bit_exact does: `point_list` and `ranges`
 under tile_cull = 0 are the reference's own lists.  Nothing is compared with the code under test.
 
-  depth-sort regimes   P = 16,385 (first size beyond the one-workgroup sort: three 11-bit passes, the counts handed on by the
-                       plain scatter), 200,000 (last size of that path), 200,001 (first size of the four 8-bit passes, the
-                       counts handed on by the scatter that reorders its chunk in LDS) - all at 272 x 256 (272 tiles: 9 bits,
-                       digits of 5 + 4)
+  depth-sort regimes   the LSD passes, asked for by depth_sort_buckets = 0 (they are the default above 1,250,000 Gaussians; up to
+                       there the default is the sort by buckets, tests/test_gpu_depth_bucket_sort.py) and confirmed by
+                       depth_sort_info: P = 16,385 (first size beyond the one-workgroup sort: three 11-bit passes, the counts
+                       handed on by the plain scatter), 200,000 (last size of that path), 200,001 (first size of the four 8-bit
+                       passes, the counts handed on by the scatter that reorders its chunk in LDS) - all at 272 x 256 (272
+                       tiles: 9 bits, digits of 5 + 4)
   tile-digit splits    256 tiles (8 bits, one pass), 255 tiles (8), 4,160 tiles (13 bits: 7 + 6, what 1080p runs),
                        8,256 tiles (14: 7 + 7), 16,512 tiles (15: 8 + 7)
   ties                 every depth key at least twice: equal keys keep ascending id through both sorts
   empty rows           a tenth of the Gaussians visible with NO tile (opacity 1e-6 under tile_cull = 1): zeros in the counts
-  sync-free            the same lists from buffers carved for a provision, the count read on the device
+  sync-free            the same lists from buffers carved for a provision, the count read on the device: the LSD passes at
+                       both regimes, the sort by buckets at 16,385
 """
 import numpy as np
 import pytest
@@ -79,6 +82,12 @@ def _oracle_lists(name):
     return _wants[name]
 
 
+def _sort_path():
+    """Which depth sort the last forward call took (f3dgs_depth_sort_info)."""
+    from diff_gaussian_rasterization import _C
+    return _C.depth_sort_info()["path"]
+
+
 def _assert_oracle_lists(name):
     scene, want = _case_scene(name), _oracle_lists(name)
     res = _raw_forward(scene)
@@ -99,7 +108,9 @@ def _assert_oracle_lists(name):
 @pytest.mark.parametrize("name", ["P16385", "P200000", "P200001"])
 def test_depth_sort_regimes_give_the_oracles_lists(name, option):
     option("tile_cull", 0)
+    option("depth_sort_buckets", 0)
     _assert_oracle_lists(name)
+    assert _sort_path() == "passes"
 
 
 @pytest.mark.parametrize("name,tiles", [("tiles256", 256), ("tiles255", 255), ("tiles4160", 4160), ("tiles8256", 8256),
@@ -162,13 +173,16 @@ def test_gaussians_without_a_tile_leave_the_lists_in_order(option):
         assert np.array_equal(got, ref)
 
 
-@pytest.mark.parametrize("name", ["P16385", "P200001"])
-def test_sync_free_provision_gives_the_oracles_lists(name, option):
+@pytest.mark.parametrize("name,buckets,path", [("P16385", 0, "passes"), ("P200001", 0, "passes"), ("P16385", 1, "buckets")],
+                         ids=["P16385", "P200001", "P16385-buckets"])
+def test_sync_free_provision_gives_the_oracles_lists(name, buckets, path, option):
     """sync_free = 1 with room to spare: every launch is sized by the provision, the kernels take the count from the device."""
     option("tile_cull", 0)
+    option("depth_sort_buckets", buckets)
     option("sync_free", 1)
     option("instance_capacity", 2 * _oracle_lists(name)["n"] + 1000)
     _assert_oracle_lists(name)
+    assert _sort_path() == path
     from diff_gaussian_rasterization import _C
     c = _C.forward_counts()
     assert c[0] == _oracle_lists(name)["n"] and c[3] == 2 * c[0] + 1000 and c[4] == 0
