@@ -1225,6 +1225,104 @@ void DensifyGather(const torch::Tensor& src_row, const torch::Tensor& kind, cons
                  "densify_gather");
 }
 
+// The model's front end (include/f3dgs.h: f3dgs_activate_forward / _backward, f3dgs_densify_stats; model_front.py).  An input
+// is `None` or a float32 HIP tensor; a non-contiguous view is copied, and so is a misaligned one where the library reads
+// with 16-byte loads (dev_f32).
+using OptT = c10::optional<torch::Tensor>;
+
+static bool given(const OptT& t) { return t.has_value() && t->defined(); }
+
+static torch::Tensor front_in(const OptT& t, const char* name, int64_t P, int64_t per_row, bool align16) {
+    if (!given(t)) return torch::Tensor();
+    TORCH_CHECK(t->is_cuda(), name, " must live on a HIP device (got ", t->device(), "): the model front end has no CPU path");
+    TORCH_CHECK(t->scalar_type() == torch::kFloat32, name, " must be float32");
+    TORCH_CHECK(t->numel() == P * per_row, name, ": ", P * per_row, " elements expected, got ", t->sizes());
+    torch::Tensor c = t->contiguous();
+    if (align16 && c.numel() && (reinterpret_cast<uintptr_t>(c.data_ptr()) & 15)) c = c.clone();
+    return c;
+}
+
+static const float* cptr(const torch::Tensor& t) { return t.defined() && t.numel() ? t.data_ptr<float>() : nullptr; }
+static float* mptr(torch::Tensor& t) { return t.defined() && t.numel() ? t.data_ptr<float>() : nullptr; }
+static OptT opt_out(const torch::Tensor& t) { return t.defined() ? OptT(t) : OptT(); }
+
+std::tuple<OptT, OptT, OptT, OptT> ActivateForward(const OptT& scaling, const OptT& rotation, const OptT& opacity, const OptT& features_dc,
+                                                   const OptT& features_rest) {
+    const OptT* first = nullptr;
+    for (const OptT* t : {&scaling, &rotation, &opacity, &features_dc})
+        if (given(*t)) { first = t; break; }
+    TORCH_CHECK(first, "activate_forward: every group is None");
+    TORCH_CHECK(given(features_dc) || !given(features_rest), "activate_forward: features_rest without features_dc");
+    TORCH_CHECK((*first)->dim() >= 1, "activate_forward: tensors are (P, ...)");
+    const int64_t P = (*first)->size(0);
+    int64_t M = 1;
+    if (given(features_rest)) {
+        TORCH_CHECK(features_rest->dim() == 3 && features_rest->size(0) == P && features_rest->size(2) == 3,
+                    "activate_forward: features_rest must be (P, M - 1, 3); got ", features_rest->sizes());
+        M = 1 + features_rest->size(1);
+    }
+    auto sc = front_in(scaling, "scaling", P, 3, false), rot = front_in(rotation, "rotation", P, 4, false),
+         op = front_in(opacity, "opacity", P, 1, false), dc = front_in(features_dc, "features_dc", P, 3, false),
+         rest = front_in(features_rest, "features_rest", P, 3 * (M - 1), false);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard((*first)->device());
+    torch::Tensor scales, rotations, opacities, shs;
+    if (sc.defined()) scales = torch::empty({P, 3}, sc.options());
+    if (rot.defined()) rotations = torch::empty({P, 4}, rot.options());
+    if (op.defined()) opacities = torch::empty(opacity->sizes(), op.options());
+    if (dc.defined()) shs = torch::empty({P, M, 3}, dc.options());
+    check_status(f3dgs_activate_forward((int)P, (int)M, cptr(sc), cptr(rot), cptr(op), cptr(dc), cptr(rest), mptr(scales), mptr(rotations),
+                                        mptr(opacities), mptr(shs), current_stream(**first)),
+                 "activate_forward");
+    return std::make_tuple(opt_out(scales), opt_out(rotations), opt_out(opacities), opt_out(shs));
+}
+
+// `want`: which of (d_scaling, d_rotation, d_opacity, d_features_dc, d_features_rest) to produce; the others come back None.
+// scales / opacities: the forward's outputs, raw_rotation: its input; an upstream gradient that is None counts as zeros.
+std::tuple<OptT, OptT, OptT, OptT, OptT> ActivateBackward(int64_t P, int64_t M, const OptT& scales, const OptT& raw_rotation,
+                                                          const OptT& opacities, const OptT& dL_dscale, const OptT& dL_drot,
+                                                          const OptT& dL_dopacity, const OptT& dL_dsh, std::array<bool, 5> want,
+                                                          const torch::Tensor& like) {
+    TORCH_CHECK(like.is_cuda(), "activate_backward: HIP tensors only");
+    TORCH_CHECK(P >= 0 && M >= 1, "activate_backward: bad sizes");
+    auto sc = front_in(scales, "scales", P, 3, false), rot = front_in(raw_rotation, "raw_rotation", P, 4, false),
+         op = front_in(opacities, "opacities", P, 1, false), gs = front_in(dL_dscale, "dL_dscale", P, 3, false),
+         gr = front_in(dL_drot, "dL_drot", P, 4, false), go = front_in(dL_dopacity, "dL_dopacity", P, 1, false),
+         gsh = front_in(dL_dsh, "dL_dsh", P, 3 * M, true);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+    auto f32 = like.options().dtype(torch::kFloat32);
+    torch::Tensor ds, dr, dop, ddc, drest;
+    if (want[0]) ds = torch::empty({P, 3}, f32);
+    if (want[1]) dr = torch::empty({P, 4}, f32);
+    if (want[2]) dop = op.defined() ? torch::empty(op.sizes(), f32) : torch::empty({P, 1}, f32);
+    if (want[3]) ddc = torch::empty({P, 1, 3}, f32);
+    if (want[4]) drest = torch::empty({P, M - 1, 3}, f32);
+    check_status(f3dgs_activate_backward((int)P, (int)M, cptr(sc), cptr(rot), cptr(op), cptr(gs), cptr(gr), cptr(go), cptr(gsh), mptr(ds),
+                                         mptr(dr), mptr(dop), mptr(ddc), mptr(drest), current_stream(like)),
+                 "activate_backward");
+    return std::make_tuple(opt_out(ds), opt_out(dr), opt_out(dop), opt_out(ddc), opt_out(drest));
+}
+
+// In place on the three accumulators (each None or a contiguous float32 HIP tensor of P elements).
+void DensifyStats(const OptT& viewspace_grad, const torch::Tensor& radii, OptT xyz_gradient_accum, OptT denom, OptT max_radii2D) {
+    TORCH_CHECK(radii.is_cuda(), "densify_stats: radii must live on a HIP device");
+    const int64_t P = radii.numel();
+    torch::Tensor r = radii.scalar_type() == torch::kInt32 ? radii.contiguous() : radii.to(torch::kInt32).contiguous();
+    torch::Tensor g = front_in(viewspace_grad, "viewspace_grad", P, 3, false);
+    float* acc[3] = {nullptr, nullptr, nullptr};
+    const OptT* in[3] = {&xyz_gradient_accum, &denom, &max_radii2D};
+    const char* names[3] = {"xyz_gradient_accum", "denom", "max_radii2D"};
+    for (int k = 0; k < 3; k++) {
+        if (!given(*in[k])) continue;
+        const torch::Tensor& t = **in[k];
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.numel() == P, "densify_stats: ", names[k],
+                    " must be a contiguous float32 HIP tensor of ", P, " elements (it is updated in place)");
+        acc[k] = P ? t.data_ptr<float>() : nullptr;
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(radii.device());
+    check_status(f3dgs_densify_stats((int)P, cptr(g), P ? r.data_ptr<int32_t>() : nullptr, acc[0], acc[1], acc[2], current_stream(radii)),
+                 "densify_stats");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -1326,6 +1424,12 @@ PYBIND11_MODULE(_C, m) {
     m.def("adam_step_multi", &AdamStepMulti, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("lrs"),
           py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("steps"), py::arg("row_mask") = py::none());
     m.def("densify_gather", &DensifyGather);
+    m.def("activate_forward", &ActivateForward, py::arg("scaling"), py::arg("rotation"), py::arg("opacity"), py::arg("features_dc"),
+          py::arg("features_rest"));
+    m.def("activate_backward", &ActivateBackward, py::arg("P"), py::arg("M"), py::arg("scales"), py::arg("raw_rotation"), py::arg("opacities"),
+          py::arg("dL_dscale"), py::arg("dL_drot"), py::arg("dL_dopacity"), py::arg("dL_dsh"), py::arg("want"), py::arg("like"));
+    m.def("densify_stats", &DensifyStats, py::arg("viewspace_grad"), py::arg("radii"), py::arg("xyz_gradient_accum"), py::arg("denom"),
+          py::arg("max_radii2D"));
     m.def("version", []() { return f3dgs_version(); });
     m.def("set_feature_grad_hook", [](py::object fn) { feature_grad_hook() = std::move(fn); },
           "callable(dL_dsemantic_feature) run inside rasterize_gaussians_backward once that tensor is final on the stream; None removes it");

@@ -56,7 +56,7 @@ def dp_train_step(render: Callable, loss_fn: Callable, model, cameras: Iterable,
                   group=None, overlap: bool = True, param_names: Sequence[str] = REFERENCE_PARAM_NAMES,
                   feature_param: str = "_semantic_feature", densification_stats: bool = True,
                   sh_params: Sequence[str] = ("_features_dc", "_features_rest"), rows_chunks: int = 4,
-                  reduce: bool = True) -> StepResult:
+                  reduce: bool = True, fused_stats: bool = False) -> StepResult:
     """Render + loss + backward for this rank's `cameras`, then make gradients and densification statistics
     global.  `render(camera, model, pipe, background)` is the reference's `gaussian_renderer.render`;
     `loss_fn(render_pkg, camera)` returns the scalar loss of one view.  The optimizer step stays with the caller
@@ -65,7 +65,9 @@ def dp_train_step(render: Callable, loss_fn: Callable, model, cameras: Iterable,
     all-reduce runs in `rows_chunks` row ranges inside the backward pass (empty: reduce them afterwards).
     `reduce=False`: the gradients stay LOCAL to the rank (the densification statistics are still made global) - for a sharded
     optimizer, whose reduce-scatter is the exchange: `dp.ShardedOptimizer(...).step(result.grads)` (half the gradient
-    bytes of the all-reduce, optimizer work and state divided by the world size)."""
+    bytes of the all-reduce, optimizer work and state divided by the world size).
+    `fused_stats`: the densification statistics through `model_front.densification_stats` (one launch per view on zeroed
+    buffers for the deltas, one more for the model's radii) instead of boolean-mask indexing: nothing is read back to the host."""
     params = {n: getattr(model, n) for n in param_names if getattr(model, n, None) is not None}
     cameras = list(cameras)
     P = next(iter(params.values())).shape[0]
@@ -99,7 +101,20 @@ def dp_train_step(render: Callable, loss_fn: Callable, model, cameras: Iterable,
                            overlap=overlap and reduce and len(cameras) == 1, feature_key=feature_param,
                            rows_leaves={"sh": tuple(sh_params)} if sh_params else None, rows_chunks=rows_chunks, reduce=reduce)
 
-    if densification_stats:
+    if densification_stats and fused_stats:
+        import model_front
+        with torch.no_grad():
+            norm = torch.zeros(P, 1, device=device)
+            count = torch.zeros(P, 1, device=device)
+            radii = torch.zeros(P, device=device, dtype=torch.float32)
+            for pkg in pkgs:        # the deltas of all views: the kernel adds into the zeroed buffers
+                model_front.densification_stats(pkg["viewspace_points"].grad, pkg["radii"], norm, count, radii)
+            dp.reduce_densification_stats(norm, count, radii, group=group)
+            model.xyz_gradient_accum += norm
+            model.denom += count
+            # the second call: max_radii2D = max(max_radii2D, radii) where a view saw the Gaussian (radii > 0), else untouched
+            model_front.densification_stats(None, radii.to(torch.int32), None, None, model.max_radii2D)
+    elif densification_stats:
         with torch.no_grad():
             norm = torch.zeros(P, 1, device=device)
             count = torch.zeros(P, 1, device=device)

@@ -891,6 +891,52 @@ int f3dgs_densify_gather(size_t n_out, const int32_t* src_row, const uint8_t* ki
                          const f3dgs_densify_tensor* tensors /* host array */, void* stream /* hipStream_t */);
 
 /*
+ * The model's front end: what stands between its raw parameters and the op (scene/gaussian_model.py:98-127: the getters
+ * get_scaling, get_rotation, get_opacity, get_features that every render() call runs, and what autograd mirrors of them), and the
+ * densification statistics behind the op (train.py:132-133, scene/gaussian_model.py:436-438).  Each entry point is ONE launch on
+ * `stream`: no host read, no memset, no allocation, no scratch - capturable.  P == 0 returns F3DGS_OK without touching the device.
+ * F3DGS_ERR_INVALID_ARGUMENT before any device work: P < 0, M < 1, a NULL input of a group whose output was requested, a
+ * misaligned pointer named below.  M > 256: F3DGS_ERR_UNSUPPORTED.  Inputs are contiguous fp32 at any 4-byte alignment.
+ *
+ * f3dgs_activate_forward: four groups, each optional - a NULL output skips the group, and its inputs may then be NULL.
+ *   scales (P,3)     = expf(raw_scaling)
+ *   rotations (P,4)  = q / max(sqrt(fp32 sum of squares), 1e-12): F.normalize's formula; it does not rescale, so its overflow
+ *                      and underflow are those of the fp32 sum
+ *   opacities (P)    = 1 / (1 + expf(-raw_opacity))
+ *   shs (P,M,3)      row i = [features_dc row i (3 floats) | features_rest row i (3 (M - 1) floats)]: a copy, bit-exact.  With
+ *                      M == 1 features_rest may be NULL.
+ *   `rotations` and `shs` must be 16-byte aligned ("Alignment" above: the op reads them with 16-byte loads, and they are written
+ *   with 16-byte stores); the split sources are read with consecutive dwords across the wave.
+ *
+ * f3dgs_activate_backward: every non-NULL output is fully overwritten; a NULL upstream gradient counts as zeros (its saved
+ * input may then be NULL).  `scales` and `opacities` are the forward's OUTPUTS, `raw_rotation` its input.
+ *   d_raw_scaling  = dL_dscale * scales
+ *   d_raw_opacity  = dL_dopacity * opacities * (1 - opacities)
+ *   d_raw_rotation: with n = ||raw_rotation|| (fp32, as in the forward): n >= 1e-12: (g - h (h . g)) / n, h = q / n; otherwise
+ *                   g / 1e-12 (the clamp was active)
+ *   d_features_dc (P,1,3), d_features_rest (P,M-1,3): the two column ranges of dL_dsh, bit-exact; each may be NULL.  dL_dsh is
+ *                   read with 16-byte loads and must be 16-byte aligned.
+ *
+ * f3dgs_densify_stats: for every i with radii[i] > 0
+ *   xyz_gradient_accum[i] += sqrt(gx^2 + gy^2), (gx, gy) = dL_dmean2D[i][0..1]; the norm and the sum are formed in fp64 and
+ *                            rounded once, so the result is the correctly rounded fp32 sum
+ *   denom[i] += 1;  max_radii2D[i] = max(max_radii2D[i], (float)radii[i])
+ * and rows with radii <= 0 are untouched.  Each accumulator may be NULL.  dL_dmean2D == NULL means zero gradients: denom and
+ * max_radii2D still update (train_step.densification_deltas with `.grad is None`).  The call ADDS into its buffers: the per-view
+ * deltas of a data-parallel step are the same call on zeroed buffers.
+ */
+int f3dgs_activate_forward(int P, int M, const float* raw_scaling /* (P,3) */, const float* raw_rotation /* (P,4) */,
+                           const float* raw_opacity /* (P) */, const float* features_dc /* (P,1,3) */,
+                           const float* features_rest /* (P,M-1,3) */, float* scales, float* rotations, float* opacities,
+                           float* shs, void* stream /* hipStream_t */);
+int f3dgs_activate_backward(int P, int M, const float* scales, const float* raw_rotation, const float* opacities,
+                            const float* dL_dscale, const float* dL_drot, const float* dL_dopacity, const float* dL_dsh,
+                            float* d_raw_scaling, float* d_raw_rotation, float* d_raw_opacity, float* d_features_dc,
+                            float* d_features_rest, void* stream /* hipStream_t */);
+int f3dgs_densify_stats(int P, const float* dL_dmean2D /* (P,3) or NULL */, const int32_t* radii /* (P) */,
+                        float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream /* hipStream_t */);
+
+/*
  * Replaces SimpleKNN::knn / distCUDA2 of the reference's second native module (submodules/simple-knn/
  * simple_knn.cu:45-221, spatial.cu:15-25; caller scene/gaussian_model.py:146): mean_dist2[i] = mean of the squared
  * distances from point i to its three nearest neighbours (exact; a missing neighbour counts as FLT_MAX, as there).
