@@ -5,6 +5,10 @@
 //     m = m + (1 - b1)(g - m);  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // The reference steps seven tensors with torch's multi-kernel foreach path; this is ONE streaming pass per tensor:
 // 16 bytes read + 12 written per element, float4-vectorised.
+//
+// The capturable form (include/f3dgs.h: f3dgs_adam_schedule + f3dgs_adam_step_multi_device) keeps t, lr and the two
+// bias-correction constants on the device: one wave advances the step words and forms the constants, the step kernel reads
+// them - so a launch replayed from a graph takes the step it runs in.  Also here: the in-place opacity reset.
 #include "common.h"
 
 namespace f3dgs {
@@ -72,12 +76,10 @@ struct AdamTable {
     int count;
 };
 
-__global__ void __launch_bounds__(256)
-adam_multi_kernel(AdamTable tab, float b2, float omb1, float omb2, float eps, const uint8_t* __restrict__ row_mask) {
-    int k = 0;
-#pragma unroll 1
-    while (k + 1 < tab.count && blockIdx.x >= tab.t[k + 1].block0) k++;
-    const AdamEntry e = tab.t[k];
+// One workgroup's share of one table entry: the float4 path, the ragged tail and the row-mask variant.  Both multi-tensor
+// kernels below go through it and differ only in where the entry's two constants come from.
+__device__ __forceinline__ void adam_entry_block(const AdamEntry& e, float step_size, float inv_sqrt_bc2, float b2, float omb1,
+                                                 float omb2, float eps, const uint8_t* __restrict__ row_mask) {
     const size_t i4 = ((size_t)(blockIdx.x - e.block0) * 256 + threadIdx.x) * 4;
     if (i4 >= e.n) return;
     float* __restrict__ p = e.p; const float* __restrict__ g = e.g; float* __restrict__ m = e.m; float* __restrict__ v = e.v;
@@ -89,7 +91,7 @@ adam_multi_kernel(AdamTable tab, float b2, float omb1, float omb2, float eps, co
         if (!any) return;
         for (size_t i = i4; i <= last; i++) {
             if (!row_mask[i / e.width]) continue;
-            adam_update(p[i], g[i], m[i], v[i], e.step_size, b2, omb1, omb2, e.inv_sqrt_bc2, eps);
+            adam_update(p[i], g[i], m[i], v[i], step_size, b2, omb1, omb2, inv_sqrt_bc2, eps);
         }
         return;
     }
@@ -99,13 +101,100 @@ adam_multi_kernel(AdamTable tab, float b2, float omb1, float omb2, float eps, co
         const float4 gg = *reinterpret_cast<const float4*>(g + i4);
         float* pa = &pp.x; float* ma = &mm.x; float* va = &vv.x; const float* ga = &gg.x;
 #pragma unroll
-        for (int q = 0; q < 4; q++) adam_update(pa[q], ga[q], ma[q], va[q], e.step_size, b2, omb1, omb2, e.inv_sqrt_bc2, eps);
+        for (int q = 0; q < 4; q++) adam_update(pa[q], ga[q], ma[q], va[q], step_size, b2, omb1, omb2, inv_sqrt_bc2, eps);
         *reinterpret_cast<float4*>(p + i4) = pp;
         *reinterpret_cast<float4*>(m + i4) = mm;
         *reinterpret_cast<float4*>(v + i4) = vv;
         return;
     }
-    for (size_t i = i4; i < e.n && i < i4 + 4; i++) adam_update(p[i], g[i], m[i], v[i], e.step_size, b2, omb1, omb2, e.inv_sqrt_bc2, eps);
+    for (size_t i = i4; i < e.n && i < i4 + 4; i++) adam_update(p[i], g[i], m[i], v[i], step_size, b2, omb1, omb2, inv_sqrt_bc2, eps);
+}
+
+// DEVICE_CONSTS = false: the constants the host formed, from the entry (f3dgs_adam_step_multi).  true: from consts[k], which
+// adam_schedule_kernel wrote earlier on the stream (f3dgs_adam_step_multi_device); k is the same for the whole workgroup, so
+// that read is a uniform (scalar) load.
+template <bool DEVICE_CONSTS>
+__device__ __forceinline__ void adam_multi_body(const AdamTable& tab, const f3dgs_adam_consts* __restrict__ consts, float b2,
+                                                float omb1, float omb2, float eps, const uint8_t* __restrict__ row_mask) {
+    int k = 0;
+#pragma unroll 1
+    while (k + 1 < tab.count && blockIdx.x >= tab.t[k + 1].block0) k++;
+    const AdamEntry e = tab.t[k];
+    float step_size = e.step_size, inv_sqrt_bc2 = e.inv_sqrt_bc2;
+    if (DEVICE_CONSTS) {
+        const f3dgs_adam_consts c = consts[k];
+        step_size = c.step_size;
+        inv_sqrt_bc2 = c.inv_sqrt_bc2;
+    }
+    adam_entry_block(e, step_size, inv_sqrt_bc2, b2, omb1, omb2, eps, row_mask);
+}
+
+__global__ void __launch_bounds__(256)
+adam_multi_kernel(AdamTable tab, float b2, float omb1, float omb2, float eps, const uint8_t* __restrict__ row_mask) {
+    adam_multi_body<false>(tab, nullptr, b2, omb1, omb2, eps, row_mask);
+}
+
+__global__ void __launch_bounds__(256)
+adam_multi_device_kernel(AdamTable tab, const f3dgs_adam_consts* __restrict__ consts, float b2, float omb1, float omb2, float eps,
+                         const uint8_t* __restrict__ row_mask) {
+    adam_multi_body<true>(tab, consts, b2, omb1, omb2, eps, row_mask);
+}
+
+// ---- step counts, rates and the two constants on the device ---------------------------------------------------------------
+// The rate of a scheduled tensor at iteration i, in fp64: log-linear from lr_init (i = 0) to lr_final (i >= max_steps), both
+// zero meaning "frozen"; scaled during the first lr_delay_steps iterations by a factor that rises from lr_delay_mult to 1
+// along a quarter sine wave.
+__device__ __forceinline__ double scheduled_rate(const f3dgs_adam_device_tensor& t, double i) {
+    if (t.lr_init == 0.0 && t.lr_final == 0.0) return 0.0;
+    double delay = 1.0;
+    if (t.lr_delay_steps > 0) {
+        const double w = fmin(fmax(i / (double)t.lr_delay_steps, 0.0), 1.0);
+        delay = t.lr_delay_mult + (1.0 - t.lr_delay_mult) * sin(1.5707963267948966 * w);
+    }
+    const double u = fmin(fmax(i / (double)t.max_steps, 0.0), 1.0);
+    return delay * exp(log(t.lr_init) * (1.0 - u) + log(t.lr_final) * u);
+}
+
+struct AdamScheduleTable {
+    f3dgs_adam_device_tensor t[F3DGS_ADAM_MAX_TENSORS];
+    int count;
+};
+
+// One wave; lane k serves table entry k.  Every lane reads the iteration word before lane 0 stores the advanced one (the
+// barrier keeps that order whatever the compiler does with the loads).
+__global__ void __launch_bounds__(64)
+adam_schedule_kernel(AdamScheduleTable tab, double b1, double b2, long long* __restrict__ iteration, int advance,
+                     f3dgs_adam_consts* __restrict__ consts) {
+    const int k = threadIdx.x;
+    long long it = 0;
+    if (iteration) it = *iteration + (advance ? 1 : 0);
+    __syncthreads();
+    if (k == 0 && iteration && advance) *iteration = it;
+    if (k >= tab.count) return;
+    const f3dgs_adam_device_tensor& e = tab.t[k];
+    if (e.n == 0) return;
+    const float t = *e.step + 1.0f;
+    *e.step = t;
+    const double lr = e.scheduled ? scheduled_rate(e, (double)it) : *e.lr;
+    // formed in double and rounded once, as launch_adam_step_multi does on the host
+    const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
+    f3dgs_adam_consts c;
+    c.lr_now = lr;
+    c.step_size = (float)(lr / bc1);
+    c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    consts[k] = c;
+}
+
+// ---- the reference's reset_opacity without a new Parameter -----------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+reset_opacity_kernel(size_t n, float* __restrict__ raw, float* __restrict__ m, float* __restrict__ v, float cap) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float s = 1.0f / (1.0f + expf(-raw[i]));          // model_front.hip's sigmoid
+    const float x = fminf(s, cap);                          // torch.min: a NaN stays a NaN
+    raw[i] = (s != s) ? s : logf(x / (1.0f - x));           // inverse_sigmoid
+    if (m) m[i] = 0.0f;
+    if (v) v[i] = 0.0f;
 }
 
 }  // namespace
@@ -131,6 +220,45 @@ void launch_adam_step_multi(int count, const f3dgs_adam_tensor* tensors, double 
     if (tab.count == 0) return;
     hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, s, tab, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2),
                        (float)eps, row_mask);
+}
+
+void launch_adam_schedule(int count, const f3dgs_adam_device_tensor* tensors, double b1, double b2, long long* iteration, int advance,
+                          f3dgs_adam_consts* consts, hipStream_t s) {
+    AdamScheduleTable tab;
+    tab.count = count;
+    bool any = false;
+    for (int i = 0; i < count; i++) {
+        tab.t[i] = tensors[i];
+        any = any || tensors[i].n != 0;
+    }
+    if (!any) return;        // nothing is stepped: no step word moves, and neither does the iteration
+    hipLaunchKernelGGL(adam_schedule_kernel, dim3(1), dim3(64), 0, s, tab, b1, b2, iteration, advance, consts);
+}
+
+void launch_adam_step_multi_device(int count, const f3dgs_adam_device_tensor* tensors, double b1, double b2, double eps,
+                                   const uint8_t* row_mask, size_t rows, const f3dgs_adam_consts* consts, hipStream_t s) {
+    // entry k stays entry k (consts[k] is its slot): an empty tensor keeps its place with no workgroups of its own
+    AdamTable tab;
+    tab.count = count;
+    uint32_t blocks = 0;
+    for (int i = 0; i < count; i++) {
+        const f3dgs_adam_device_tensor& t = tensors[i];
+        AdamEntry& e = tab.t[i];
+        e.p = t.param; e.g = t.grad; e.m = t.exp_avg; e.v = t.exp_avg_sq; e.n = t.n;
+        e.block0 = blocks;
+        e.width = (row_mask && rows && t.n && t.n % rows == 0) ? (uint32_t)(t.n / rows) : 0u;
+        e.step_size = 0.f;
+        e.inv_sqrt_bc2 = 0.f;
+        blocks += (uint32_t)(((t.n + 3) / 4 + 255) / 256);
+    }
+    if (blocks == 0) return;
+    hipLaunchKernelGGL(adam_multi_device_kernel, dim3(blocks), dim3(256), 0, s, tab, consts, (float)b2, (float)(1.0 - b1),
+                       (float)(1.0 - b2), (float)eps, row_mask);
+}
+
+void launch_reset_opacity(size_t n, float* raw, float* exp_avg, float* exp_avg_sq, float cap, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(reset_opacity_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, n, raw, exp_avg, exp_avg_sq, cap);
 }
 
 void launch_adam_step(size_t n, float* p, const float* g, float* m, float* v, double lr, double b1, double b2, double eps, int step,

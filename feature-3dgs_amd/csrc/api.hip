@@ -423,7 +423,7 @@ CountReadback* count_readback(hipStream_t s, bool may_create) {
 
 extern "C" {
 
-int f3dgs_version(void) { return 32300; }   // 3.23.0 (major * 10000 + minor * 100 + patch): 3.23 f3dgs_activate_forward, f3dgs_activate_backward, f3dgs_densify_stats; 3.22 f3dgs_codebook_assign, f3dgs_codebook_update; 3.21 f3dgs_transform_gaussians; 3.20 f3dgs_group_stats, f3dgs_group_merge; 3.19 f3dgs_knn_components, f3dgs_component_filter; 3.18 f3dgs_knn_neighbors, f3dgs_label_mode_filter, option knn_outward; 3.17 f3dgs_instance_associate, f3dgs_instance_merge; 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
+int f3dgs_version(void) { return 32400; }   // 3.23.0 (major * 10000 + minor * 100 + patch): 3.23 f3dgs_activate_forward, f3dgs_activate_backward, f3dgs_densify_stats; 3.22 f3dgs_codebook_assign, f3dgs_codebook_update; 3.21 f3dgs_transform_gaussians; 3.20 f3dgs_group_stats, f3dgs_group_merge; 3.19 f3dgs_knn_components, f3dgs_component_filter; 3.18 f3dgs_knn_neighbors, f3dgs_label_mode_filter, option knn_outward; 3.17 f3dgs_instance_associate, f3dgs_instance_merge; 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
 
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 
@@ -1155,6 +1155,73 @@ int f3dgs_adam_step_multi(int n_tensors, const f3dgs_adam_tensor* tensors, doubl
     if (blocks >= (1ull << 31)) return fail(F3DGS_ERR_UNSUPPORTED, "too large for one launch");
     if (row_mask && rows == 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "row mask without a row count");
     launch_adam_step_multi(n_tensors, tensors, beta1, beta2, eps, row_mask, rows, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+// The checks f3dgs_adam_schedule and f3dgs_adam_step_multi_device share: both take the same table.
+static int check_adam_device_table(const char* who, int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2,
+                                   const void* consts, size_t* blocks_out) {
+    if (n_tensors < 0 || n_tensors > F3DGS_ADAM_MAX_TENSORS)
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: 0 .. %d tensors per call", who, F3DGS_ADAM_MAX_TENSORS);
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
+    *blocks_out = 0;
+    if (n_tensors == 0) return F3DGS_OK;
+    if (!tensors) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null table", who);
+    if (!consts) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null table of constants", who);
+    if (reinterpret_cast<uintptr_t>(consts) & 7) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: the table of constants must be 8-byte aligned", who);
+    size_t blocks = 0;
+    for (int i = 0; i < n_tensors; i++) {
+        const f3dgs_adam_device_tensor& t = tensors[i];
+        if (t.scheduled) {
+            if (t.max_steps <= 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: max_steps = %lld", who, i, t.max_steps);
+            if (t.lr_delay_steps < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: lr_delay_steps = %lld", who, i, t.lr_delay_steps);
+            if (!(t.lr_init >= 0.0) || !(t.lr_final >= 0.0) || ((t.lr_init == 0.0) != (t.lr_final == 0.0)))
+                return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: rates %g -> %g: both positive or both zero", who, i, t.lr_init, t.lr_final);
+        }
+        if (t.n == 0) continue;
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null pointer", who, i);
+        if (!t.step) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null step word", who, i);
+        if (!t.scheduled && !t.lr) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null rate word", who, i);
+        blocks += ((t.n + 3) / 4 + 255) / 256;
+    }
+    if (blocks >= (1ull << 31)) return fail(F3DGS_ERR_UNSUPPORTED, "%s: too large for one launch", who);
+    *blocks_out = blocks;
+    return F3DGS_OK;
+}
+
+int f3dgs_adam_schedule(int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2, long long* iteration,
+                        int advance, f3dgs_adam_consts* consts, void* stream) {
+    size_t blocks = 0;
+    if (int rc = check_adam_device_table("f3dgs_adam_schedule", n_tensors, tensors, beta1, beta2, consts, &blocks)) return rc;
+    if (n_tensors == 0) return F3DGS_OK;
+    for (int i = 0; i < n_tensors; i++)
+        if (tensors[i].scheduled && !iteration)
+            return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_schedule: tensor %d is scheduled, but there is no iteration word", i);
+    if (reinterpret_cast<uintptr_t>(iteration) & 7) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_schedule: misaligned iteration word");
+    launch_adam_schedule(n_tensors, tensors, beta1, beta2, iteration, advance, consts, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+int f3dgs_adam_step_multi_device(int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2, double eps,
+                                 const uint8_t* row_mask, size_t rows, const f3dgs_adam_consts* consts, void* stream) {
+    size_t blocks = 0;
+    if (int rc = check_adam_device_table("f3dgs_adam_step_multi_device", n_tensors, tensors, beta1, beta2, consts, &blocks)) return rc;
+    if (row_mask && rows == 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_step_multi_device: row mask without a row count");
+    if (n_tensors == 0) return F3DGS_OK;
+    launch_adam_step_multi_device(n_tensors, tensors, beta1, beta2, eps, row_mask, rows, consts, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+int f3dgs_reset_opacity(size_t n, float* raw, float* exp_avg, float* exp_avg_sq, float cap, void* stream) {
+    if (!(cap > 0.f && cap < 1.f)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_reset_opacity: cap = %g outside (0, 1)", (double)cap);
+    if (n == 0) return F3DGS_OK;
+    if (!raw) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_reset_opacity: null pointer");
+    if (n >= (1ull << 39)) return fail(F3DGS_ERR_UNSUPPORTED, "f3dgs_reset_opacity: too large for one launch");
+    launch_reset_opacity(n, raw, exp_avg, exp_avg_sq, cap, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return F3DGS_OK;
 }

@@ -1187,6 +1187,87 @@ void AdamStepMulti(std::vector<torch::Tensor> params, std::vector<torch::Tensor>
     check_status(f3dgs_adam_step_multi((int)n, tab, beta1, beta2, eps, mask, rows, current_stream(params[0])), "adam_step_multi");
 }
 
+// The capturable step (include/f3dgs.h: f3dgs_adam_schedule + f3dgs_adam_step_multi_device): step counts, rates and the two
+// constants live on the device.  steps[i]: float32 scalar; lr_table: float64, tensor i's base rate at lr_slots[i];
+// schedules[i]: empty, or {lr_init, lr_final, lr_delay_steps, lr_delay_mult, max_steps}; iteration: int64 scalar (or None);
+// consts: float64 (F3DGS_ADAM_MAX_TENSORS, 2) - column 0 is the rate used, column 1 holds the two fp32 constants.
+// `phases`: 1 the schedule launch only, 2 the step launch only, 3 both.
+void AdamStepMultiDevice(std::vector<torch::Tensor> params, std::vector<torch::Tensor> grads, std::vector<torch::Tensor> exp_avgs,
+                         std::vector<torch::Tensor> exp_avg_sqs, std::vector<torch::Tensor> steps, const torch::Tensor& lr_table,
+                         std::vector<int64_t> lr_slots, std::vector<std::vector<double>> schedules, double beta1, double beta2,
+                         double eps, const c10::optional<torch::Tensor>& iteration, bool advance, torch::Tensor& consts,
+                         const c10::optional<torch::Tensor>& row_mask, int64_t phases) {
+    const char* who = "adam_step_multi_device";
+    const size_t n = params.size();
+    TORCH_CHECK(n <= F3DGS_ADAM_MAX_TENSORS, who, ": at most ", F3DGS_ADAM_MAX_TENSORS, " tensors per call");
+    TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n && steps.size() == n && lr_slots.size() == n &&
+                schedules.size() == n, who, ": list lengths differ");
+    if (n == 0) return;
+    TORCH_CHECK(lr_table.is_cuda() && lr_table.scalar_type() == torch::kFloat64 && lr_table.is_contiguous(), who, ": lr_table must be a contiguous float64 HIP tensor");
+    TORCH_CHECK(consts.is_cuda() && consts.scalar_type() == torch::kFloat64 && consts.is_contiguous() &&
+                consts.numel() == 2 * F3DGS_ADAM_MAX_TENSORS, who, ": consts must be a contiguous float64 HIP tensor of ", 2 * F3DGS_ADAM_MAX_TENSORS, " elements");
+    static_assert(sizeof(f3dgs_adam_consts) == 2 * sizeof(double), "consts layout");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(params[0].device());
+    std::vector<torch::Tensor> keep;       // contiguous copies of gradients stay alive until the launch is enqueued
+    f3dgs_adam_device_tensor tab[F3DGS_ADAM_MAX_TENSORS];
+    for (size_t i = 0; i < n; i++) {
+        TORCH_CHECK(params[i].is_cuda() && grads[i].is_cuda() && exp_avgs[i].is_cuda() && exp_avg_sqs[i].is_cuda() && steps[i].is_cuda(), who, ": HIP tensors only");
+        TORCH_CHECK(params[i].scalar_type() == torch::kFloat32 && grads[i].scalar_type() == torch::kFloat32, who, ": float32 only");
+        TORCH_CHECK(steps[i].scalar_type() == torch::kFloat32 && steps[i].numel() == 1, who, ": the step word is one float32");
+        TORCH_CHECK(params[i].is_contiguous() && exp_avgs[i].is_contiguous() && exp_avg_sqs[i].is_contiguous(), who, ": contiguous state");
+        TORCH_CHECK(grads[i].numel() == params[i].numel() && exp_avgs[i].numel() == params[i].numel() &&
+                    exp_avg_sqs[i].numel() == params[i].numel(), who, ": size mismatch");
+        TORCH_CHECK(lr_slots[i] >= 0 && lr_slots[i] < lr_table.numel(), who, ": lr slot outside the table");
+        TORCH_CHECK(schedules[i].empty() || schedules[i].size() == 5, who, ": a schedule is (lr_init, lr_final, lr_delay_steps, lr_delay_mult, max_steps)");
+        keep.push_back(grads[i].contiguous());
+        f3dgs_adam_device_tensor& t = tab[i];
+        t = f3dgs_adam_device_tensor{};
+        t.param = params[i].data_ptr<float>(); t.grad = keep.back().data_ptr<float>();
+        t.exp_avg = exp_avgs[i].data_ptr<float>(); t.exp_avg_sq = exp_avg_sqs[i].data_ptr<float>();
+        t.n = (size_t)params[i].numel();
+        t.step = steps[i].data_ptr<float>();
+        t.lr = lr_table.data_ptr<double>() + lr_slots[i];
+        if (!schedules[i].empty()) {
+            const auto& sc = schedules[i];
+            t.scheduled = 1;
+            t.lr_init = sc[0]; t.lr_final = sc[1]; t.lr_delay_steps = (long long)sc[2]; t.lr_delay_mult = sc[3]; t.max_steps = (long long)sc[4];
+        }
+    }
+    long long* it = nullptr;
+    if (iteration.has_value() && iteration->defined()) {
+        TORCH_CHECK(iteration->is_cuda() && iteration->scalar_type() == torch::kInt64 && iteration->numel() == 1, who, ": the iteration word is one int64 on the device");
+        it = reinterpret_cast<long long*>(iteration->data_ptr<int64_t>());
+    }
+    const uint8_t* mask = nullptr;
+    size_t rows = 0;
+    torch::Tensor mk;
+    if (row_mask.has_value() && row_mask->defined()) {
+        TORCH_CHECK(row_mask->is_cuda(), who, ": the mask must be a HIP tensor");
+        mk = mask_bytes(*row_mask);
+        mask = static_cast<const uint8_t*>(mk.data_ptr());
+        rows = (size_t)mk.numel();
+    }
+    auto* cs = reinterpret_cast<f3dgs_adam_consts*>(consts.data_ptr<double>());
+    if (phases & 1) check_status(f3dgs_adam_schedule((int)n, tab, beta1, beta2, it, advance ? 1 : 0, cs, current_stream(params[0])), who);
+    if (phases & 2) check_status(f3dgs_adam_step_multi_device((int)n, tab, beta1, beta2, eps, mask, rows, cs, current_stream(params[0])), who);
+}
+
+// The reference's reset_opacity in place (include/f3dgs.h: f3dgs_reset_opacity); the moments may be None.
+void ResetOpacity(torch::Tensor& raw, const c10::optional<torch::Tensor>& exp_avg, const c10::optional<torch::Tensor>& exp_avg_sq, double cap) {
+    TORCH_CHECK(raw.is_cuda() && raw.scalar_type() == torch::kFloat32 && raw.is_contiguous(), "reset_opacity: a contiguous float32 HIP tensor expected");
+    float* mv[2] = {nullptr, nullptr};
+    const c10::optional<torch::Tensor>* in[2] = {&exp_avg, &exp_avg_sq};
+    for (int k = 0; k < 2; k++) {
+        if (!in[k]->has_value() || !(*in[k])->defined()) continue;
+        const torch::Tensor& t = **in[k];
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.numel() == raw.numel(), "reset_opacity: the moments must match the parameter");
+        mv[k] = t.numel() ? t.data_ptr<float>() : nullptr;
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(raw.device());
+    check_status(f3dgs_reset_opacity((size_t)raw.numel(), raw.numel() ? raw.data_ptr<float>() : nullptr, mv[0], mv[1], (float)cap, current_stream(raw)),
+                 "reset_opacity");
+}
+
 // One gather over all per-Gaussian tensors (densify.py builds the plan).  `modes[i]`: F3DGS_DENSIFY_*;
 // `overrides[i]` is the child-row array for mode OVERRIDE_CHILD (an empty tensor otherwise).
 void DensifyGather(const torch::Tensor& src_row, const torch::Tensor& kind, const torch::Tensor& override_row,
@@ -1423,6 +1504,10 @@ PYBIND11_MODULE(_C, m) {
           py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("step"), py::arg("row_mask") = py::none());
     m.def("adam_step_multi", &AdamStepMulti, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("lrs"),
           py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("steps"), py::arg("row_mask") = py::none());
+    m.def("adam_step_multi_device", &AdamStepMultiDevice, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
+          py::arg("steps"), py::arg("lr_table"), py::arg("lr_slots"), py::arg("schedules"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+          py::arg("iteration"), py::arg("advance"), py::arg("consts"), py::arg("row_mask") = py::none(), py::arg("phases") = 3);
+    m.def("reset_opacity", &ResetOpacity, py::arg("raw"), py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("cap"));
     m.def("densify_gather", &DensifyGather);
     m.def("activate_forward", &ActivateForward, py::arg("scaling"), py::arg("rotation"), py::arg("opacity"), py::arg("features_dc"),
           py::arg("features_rest"));

@@ -443,6 +443,12 @@ void launch_adam_step(size_t n, float* p, const float* g, float* m, float* v, do
 void launch_adam_step_multi(int count, const f3dgs_adam_tensor* tensors, double b1, double b2, double eps, const uint8_t* row_mask,
                             size_t rows, hipStream_t s);
 
+void launch_adam_schedule(int count, const f3dgs_adam_device_tensor* tensors, double b1, double b2, long long* iteration, int advance,
+                          f3dgs_adam_consts* consts, hipStream_t s);
+void launch_adam_step_multi_device(int count, const f3dgs_adam_device_tensor* tensors, double b1, double b2, double eps,
+                                   const uint8_t* row_mask, size_t rows, const f3dgs_adam_consts* consts, hipStream_t s);
+void launch_reset_opacity(size_t n, float* raw, float* exp_avg, float* exp_avg_sq, float cap, hipStream_t s);
+
 // densify.hip
 using DensifyTensor = f3dgs_densify_tensor;
 constexpr int DENSIFY_MAX_TENSORS = F3DGS_DENSIFY_MAX_TENSORS;

@@ -125,6 +125,18 @@ def densification_stats(viewspace_grad, radii, xyz_gradient_accum, denom, max_ra
     _C.densify_stats(viewspace_grad, radii, xyz_gradient_accum, denom, max_radii2D)
 
 
+def reset_opacity_(model, cap=0.01):
+    """The reference's reset_opacity (scene/gaussian_model.py:231-234) IN PLACE, one launch: `model._opacity` becomes
+    inverse_sigmoid(min(sigmoid(_opacity), cap)) and the Adam moments of its optimizer group become zero; the step count stays.
+    The reference registers a new Parameter; here `model._opacity` keeps its identity and its address, so a captured iteration
+    (train_step.CapturedTrainer) stays valid.  Works with either mode of FusedAdam, and without an optimizer."""
+    p = model._opacity
+    opt = getattr(model, "optimizer", None)
+    st = opt.state.get(p, {}) if opt is not None else {}
+    with torch.no_grad():
+        _C.reset_opacity(p.detach(), st.get("exp_avg"), st.get("exp_avg_sq"), float(cap))
+
+
 def add_densification_stats(model, render_pkg):
     """train.py:132-133 in one launch:  max_radii2D[vis] = max(max_radii2D[vis], radii[vis])  and
     add_densification_stats(viewspace_points, vis)  (scene/gaussian_model.py:436-438) for a render_pkg after its backward."""

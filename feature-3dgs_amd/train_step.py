@@ -195,3 +195,159 @@ def dp_train_step_bands(render: Callable, loss_fn: Callable, model, camera, pipe
             mr = model.max_radii2D
             mr[seen] = torch.maximum(mr[seen], radii[seen].to(mr.dtype))
     return StepResult(loss.detach(), 1, grads)
+
+
+class CapturedTrainer:
+    """One WHOLE training iteration replayed from a HIP graph: the body of train.py:77-149 with nothing returning
+    to the host -
+
+        zero_grad(set_to_none=True); render; loss_fn(render_pkg, *targets); backward; add_densification_stats;
+        model.optimizer.step(); the decoder's optimizer, if one was given
+
+    `model.optimizer` must be a `FusedAdam(capturable=True)`: its step counts, rates and schedule live on the device, so a
+    replay takes the step it runs in.  `step(camera, *targets)` returns the detached loss and `radii` (static tensors of the
+    graph: valid until the next `step`); `render_pkg` and every parameter's `.grad` are those of the last replay.
+
+    Graphs are built with `graph_step.CapturedStep` and cached by everything a capture freezes: image size, FoVx / FoVy,
+    `active_sh_degree`, the addresses and row count of the model's parameters and statistics, the background's address, the targets' shapes
+    and the optimizer's `schedule_epoch`.  View matrices, camera centre and targets are copied into static tensors before a
+    replay, so cameras that differ only in pose share one graph.  A changed key captures again (least recently used graph
+    evicted at `max_graphs`): `densify` needs no notification - it moves the parameters, and that changes the key;
+    `model_front.reset_opacity_` keeps the addresses and so the graph.  The warm-up iterations a capture needs are undone:
+    parameters, optimizer state and densification statistics are saved before them and written back in place.
+
+    `check()` (it synchronises) is `CapturedStep.check()` for the graph last replayed: False says that the frames since the
+    last check did not fit the instance provision - their iterations stepped on incomplete gradients - and that the graph was
+    captured again with room.  `loss_fn` and `render` may call the rasterizer once per iteration (CapturedStep's rule)."""
+
+    def __init__(self, model, loss_fn: Callable, pipe, background: torch.Tensor, render: Optional[Callable] = None,
+                 max_graphs: int = 4, visibility: bool = False, decoder_optimizer=None,
+                 param_names: Sequence[str] = REFERENCE_PARAM_NAMES):
+        import model_front
+        opt = getattr(model, "optimizer", None)
+        if opt is None or not getattr(opt, "capturable", False):
+            raise TypeError("CapturedTrainer: model.optimizer must be a FusedAdam(capturable=True) - a host-side step count "
+                            "would be frozen into the graph")
+        self.model, self.loss_fn, self.pipe, self.background = model, loss_fn, pipe, background
+        self.render = render if render is not None else model_front.render
+        self.max_graphs = max(1, int(max_graphs))
+        self.visibility = bool(visibility)
+        self.decoder_optimizer = decoder_optimizer
+        self.param_names = tuple(param_names)
+        self.captures = 0
+        self.render_pkg = None
+        self._graphs = {}          # key -> entry, in order of last use (dicts keep insertion order)
+        self._stream = None        # one capture stream for every graph: the parameters' gradient accumulators stay on it
+        self._current = None
+
+    # -- what a capture freezes ---------------------------------------------------------------------------------------------------
+    def _params(self):
+        return {n: getattr(self.model, n) for n in self.param_names if getattr(self.model, n, None) is not None}
+
+    def _key(self, camera, targets):
+        params = self._params()
+        return (int(camera.image_height), int(camera.image_width), float(camera.FoVx), float(camera.FoVy),
+                int(self.model.active_sh_degree), tuple((n, p.data_ptr(), tuple(p.shape)) for n, p in params.items()),
+                tuple(getattr(self.model, n).data_ptr() for n in ("xyz_gradient_accum", "denom", "max_radii2D")),
+                self.background.data_ptr(), tuple((tuple(t.shape), t.dtype) for t in targets),
+                self.model.optimizer.schedule_epoch)
+
+    # -- state the warm-up iterations of a capture must not leave changed --------------------------------------------------------
+    def _mutable_state(self):
+        out = [p.detach() for p in self._params().values()]
+        out += self.model.optimizer.device_state()
+        out += [getattr(self.model, n) for n in ("xyz_gradient_accum", "denom", "max_radii2D")]
+        dec = self.decoder_optimizer
+        if dec is not None:
+            for g in dec.param_groups:
+                out += [p.detach() for p in g["params"]]
+            for st in dec.state.values():
+                out += [v for v in st.values() if torch.is_tensor(v)]
+        return [t for t in out if t.numel()]
+
+    @staticmethod
+    def _slot(t):
+        return (t.data_ptr(), t.numel(), t.dtype)
+
+    def _capture_keeping_state(self, capture):
+        saved = {self._slot(t): t.clone() for t in self._mutable_state()}
+        try:
+            return capture()
+        finally:
+            with torch.no_grad():
+                for t in self._mutable_state():       # state the warm-up created (a first ever step) goes back to zeros
+                    old = saved.get(self._slot(t))
+                    t.copy_(old) if old is not None else t.zero_()
+            self.captures += 1
+
+    def _build(self, camera, targets):
+        import types
+        import model_front
+        from graph_step import CapturedStep
+        cam = types.SimpleNamespace(image_height=int(camera.image_height), image_width=int(camera.image_width),
+                                    FoVx=float(camera.FoVx), FoVy=float(camera.FoVy),
+                                    world_view_transform=camera.world_view_transform.detach().clone(),
+                                    full_proj_transform=camera.full_proj_transform.detach().clone(),
+                                    camera_center=camera.camera_center.detach().clone())
+        static_targets = [t.detach().clone() for t in targets]
+        model, opt, dec = self.model, self.model.optimizer, self.decoder_optimizer
+        held = {}
+
+        def iteration():
+            opt.zero_grad(set_to_none=True)
+            if dec is not None:
+                dec.zero_grad(set_to_none=True)
+            pkg = self.render(cam, model, self.pipe, self.background)
+            loss = self.loss_fn(pkg, *static_targets)
+            loss.backward()
+            model_front.add_densification_stats(model, pkg)
+            opt.step(visibility=pkg["radii"] if self.visibility else None)
+            if dec is not None:
+                dec.step()
+            held["grads"] = {n: p.grad for n, p in self._params().items()}
+            return loss.detach(), pkg
+
+        if self._stream is None:
+            self._stream = torch.cuda.Stream()
+        step = CapturedStep(iteration, stream=self._stream)
+        self._capture_keeping_state(step.capture)
+        return types.SimpleNamespace(step=step, camera=cam, targets=static_targets, held=held)
+
+    def step(self, camera, *targets):
+        key = self._key(camera, targets)
+        entry = self._graphs.pop(key, None)
+        if entry is None:
+            entry = self._build(camera, targets)
+            while len(self._graphs) >= self.max_graphs:
+                self._graphs.pop(next(iter(self._graphs)))
+        self._graphs[key] = entry
+        self._current = entry
+        # pose and targets into the graph's static tensors: ONE multi-tensor copy launch; a target that already IS the static
+        # tensor (`static_targets`: a data loader may write there directly) costs nothing
+        pairs = [(getattr(entry.camera, n), getattr(camera, n)) for n in ("world_view_transform", "full_proj_transform", "camera_center")]
+        pairs += [(d, s) for d, s in zip(entry.targets, targets) if d.data_ptr() != s.data_ptr()]
+        with torch.no_grad():
+            if all(d.dtype == s.dtype and d.device == s.device and d.shape == s.shape for d, s in pairs):
+                torch._foreach_copy_([d for d, _ in pairs], [s for _, s in pairs])
+            else:
+                for d, s in pairs:
+                    d.copy_(s)
+        loss, pkg = entry.step.replay()
+        params = self._params()
+        for n, g in entry.held["grads"].items():        # the gradients this graph writes (another graph's may be attached)
+            params[n].grad = g
+        self.render_pkg = pkg
+        return loss, pkg["radii"]
+
+    @property
+    def static_targets(self):
+        """The target tensors the graph last replayed reads: `step` skips the copy of a target that is one of these."""
+        return None if self._current is None else list(self._current.targets)
+
+    def check(self) -> bool:
+        if self._current is None:
+            return True
+        c = self._current.step.counts()
+        if c is None or (c[4] == 0 and c[0] <= c[3]):
+            return True
+        return self._capture_keeping_state(self._current.step.check)

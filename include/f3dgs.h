@@ -868,6 +868,68 @@ int f3dgs_adam_step_multi(int n_tensors, const f3dgs_adam_tensor* tensors /* hos
                           const uint8_t* row_mask, size_t rows, void* stream);
 
 /*
+ * The capturable optimizer step (ABI 3.24): the same update with step counts, learning rates and the two bias-correction
+ * constants held on the DEVICE, so that a launch captured in a HIP graph does the step of the replay it runs in, not of the
+ * step it was captured at.  Two launches, in this order on one stream:
+ *
+ * f3dgs_adam_schedule: one wave; entry k of the table (n > 0) gets
+ *   t = *step + 1, stored back to *step (a float32 word, the layout of torch.optim.Adam(capturable=True): exact up to 2^24)
+ *   lr = scheduled ? schedule(i) : *lr, where i is the iteration this step belongs to: *iteration + 1 with `advance` != 0 (one
+ *        lane then stores i to *iteration, after every entry has read the word), *iteration itself with advance == 0 (the second
+ *        table of a step whose first table advanced the word)
+ *   consts[k] = { lr, (float)(lr / (1 - beta1^t)), (float)(1 / sqrt(1 - beta2^t)) }: both constants formed in fp64 and rounded
+ *        once, as f3dgs_adam_step_multi forms them on the host
+ *   schedule(i) = 0 if lr_init == lr_final == 0, otherwise delay * exp(log(lr_init) (1 - u) + log(lr_final) u) with
+ *        u = clip(i / max_steps, 0, 1) and delay = lr_delay_mult + (1 - lr_delay_mult) sin(pi/2 clip(i / lr_delay_steps, 0, 1))
+ *        for lr_delay_steps > 0, else 1 (the reference's get_expon_lr_func, utils/general_utils.py:29-61), in fp64.
+ *   An entry with n == 0 is left alone (step word, consts[k]); a table without any n > 0 launches nothing and advances nothing.
+ *   `iteration` may be NULL if no entry is scheduled (advance is then ignored).
+ *
+ * f3dgs_adam_step_multi_device: f3dgs_adam_step_multi's launch, with entry k's two constants read from consts[k] (what the
+ * schedule call wrote for the SAME table); `row_mask` / `rows` as there.  With equal constants it stores the same bits.
+ *
+ * `consts` holds F3DGS_ADAM_MAX_TENSORS entries of device memory, 8-byte aligned; step / lr / iteration words are device memory
+ * too.  No host read, no memset, no allocation, no scratch: everything is enqueued on `stream`.
+ * Errors (F3DGS_ERR_INVALID_ARGUMENT, nothing launched): n_tensors outside 0 .. F3DGS_ADAM_MAX_TENSORS, a null table or null
+ * `consts` (n_tensors > 0), an entry with n > 0 and a null pointer, a null step word or (not scheduled) a null lr word, a
+ * scheduled entry without `iteration`, a schedule with max_steps <= 0, lr_delay_steps < 0, exactly one of lr_init / lr_final
+ * zero or either negative (or NaN), beta1 or beta2 outside [0, 1), a mask with rows == 0.
+ */
+typedef struct {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    size_t n;                /* elements */
+    float* step;             /* device: steps taken so far, as float32 */
+    const double* lr;        /* device: the base rate (read if !scheduled) */
+    int scheduled;           /* non-zero: the rate is the schedule below */
+    double lr_init, lr_final, lr_delay_mult;
+    long long lr_delay_steps, max_steps;
+} f3dgs_adam_device_tensor;
+typedef struct {
+    double lr_now;           /* the rate this step used: for the host to read back */
+    float step_size;         /* (float)(lr_now / (1 - beta1^t)) */
+    float inv_sqrt_bc2;      /* (float)(1 / sqrt(1 - beta2^t)) */
+} f3dgs_adam_consts;
+int f3dgs_adam_schedule(int n_tensors, const f3dgs_adam_device_tensor* tensors /* host array */, double beta1, double beta2,
+                        long long* iteration /* device, or NULL */, int advance, f3dgs_adam_consts* consts /* device */,
+                        void* stream /* hipStream_t */);
+int f3dgs_adam_step_multi_device(int n_tensors, const f3dgs_adam_device_tensor* tensors /* host array */, double beta1, double beta2,
+                                 double eps, const uint8_t* row_mask, size_t rows, const f3dgs_adam_consts* consts /* device */,
+                                 void* stream /* hipStream_t */);
+
+/*
+ * The reference's reset_opacity (scene/gaussian_model.py:231-234) IN PLACE, one launch over n elements:
+ *   raw = logit(min(sigmoid(raw), cap)), sigmoid(x) = 1 / (1 + expf(-x)) (f3dgs_activate_forward's), logit(x) = logf(x / (1 - x))
+ *   (the reference's inverse_sigmoid), fp32; a NaN stays a NaN, as through torch.min
+ *   exp_avg = exp_avg_sq = 0 (each may be NULL: no optimizer state yet); a step word is not this call's business
+ * The reference builds a new Parameter instead; here the addresses survive, and with them a captured iteration.
+ * Errors (F3DGS_ERR_INVALID_ARGUMENT, nothing launched): raw == NULL with n > 0, cap outside (0, 1) or NaN.
+ */
+int f3dgs_reset_opacity(size_t n, float* raw, float* exp_avg, float* exp_avg_sq, float cap, void* stream /* hipStream_t */);
+
+/*
  * Row movement of one densification (scene/gaussian_model.py:300-431: densify_and_clone, densify_and_split,
  * prune_points and the optimizer-state edits of cat_tensors_to_optimizer / _prune_optimizer) as ONE gather over all
  * per-Gaussian tensors.  Output row j of every tensor comes from source row src_row[j]; kind[j] says how:
