@@ -17,7 +17,8 @@
 // sort starts from id order and both sorts are stable (Q6 in SURVEY.md section 8a).
 //
 // Radix pass = 3 launches: per-workgroup digit histogram, per-digit row scan (grid = digits),
-// stable scatter (wave-level match with ballots, wave-ordered LDS counters).
+// stable scatter (wave-level match with ballots, wave-ordered LDS counters).  The bucket pass of the depth sort is the same three
+// with its own layouts (template parameter BUCKET): the histogram matrix row-major with a column scan, the output as pairs.
 
 #include <atomic>
 #include "common.h"
@@ -113,7 +114,7 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_hist_kernel(const uint32_t
                                                                   uint32_t* __restrict__ ctl) {
     constexpr int BINS = 1 << BITS;
     constexpr int CHUNK = SORT_THREADS * ITEMS;
-    __shared__ uint32_t h[BINS];
+    __shared__ __attribute__((aligned(BUCKET ? 16 : 4))) uint32_t h[BINS];       // (BUCKET: read back 16 bytes at a time)
     // n_dev (sync-free forward): the launch is sized by a CAPACITY n, the item count is the device's word; workgroups behind the
     // last item write their zero column of the histogram matrix and nothing else.  A count above the capacity reads as ZERO: the
     // emit kernel stored nothing for such a frame (the arrays hold what the allocator left there), the tile ranges stay empty
@@ -132,6 +133,8 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_hist_kernel(const uint32_t
     if constexpr (BUCKET) {
         __shared__ uint32_t shk[2][SORT_THREADS / 64];
         uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+        // (the loop compiles to two steps a round trip, eight in a row at c3; all its loads in one run, and no reduction at all -
+        // a stale range, timing only - both left the stage where it was: profiles/depth_bucket_sort.md 8)
         for (int i = threadIdx.x; i < tj.n_partial; i += SORT_THREADS) {
             lo = min(lo, tj.partial[3 * tj.n_partial + i]);
             hi = max(hi, tj.partial[4 * tj.n_partial + i]);
@@ -158,7 +161,65 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_hist_kernel(const uint32_t
         if (i < n) atomicAdd(&h[d], 1u);
     }
     __syncthreads();
-    for (int d = threadIdx.x; d < BINS; d += SORT_THREADS) hist[(size_t)d * nb + blockIdx.x] = h[d];  // digit-major
+    if constexpr (BUCKET) {
+        // row-major, hist[block * BINS + d]: the workgroup's counts are one contiguous row, written with 16-byte stores (digit-major,
+        // every one of its 1,024 words went out alone, 4 nb bytes from the next); radix_colscan_kernel scans the columns
+        static_assert(BINS % (4 * SORT_THREADS) == 0, "whole 16-byte stores per thread");
+        uint4* const row = reinterpret_cast<uint4*>(hist + (size_t)blockIdx.x * BINS);
+        const uint4* const h4 = reinterpret_cast<const uint4*>(h);
+        for (int q = threadIdx.x; q < BINS / 4; q += SORT_THREADS) row[q] = h4[q];
+    } else {
+        for (int d = threadIdx.x; d < BINS; d += SORT_THREADS) hist[(size_t)d * nb + blockIdx.x] = h[d];  // digit-major
+    }
+}
+
+// The bucket pass's scan: exclusive prefixes over the workgroups (rows) of every bin (column) of the row-major matrix, in place,
+// and the column totals to totals[d].  A workgroup owns COLSCAN_BINS = 16 bins - one 64-byte sector of every row; thread (bin lane,
+// row lane) owns a run of up to COLSCAN_RUN consecutive rows: all its loads are requested before the first add, the 16 run totals
+// of a bin meet in LDS behind one barrier.  c3 (489 rows) is one sweep of 16 x 31 rows; longer matrices (c4 under option 1: 977
+// rows) go on in further sweeps of up to COLSCAN_SWEEP_ROWS rows, the columns' sums so far carried along.
+__global__ void __launch_bounds__(COLSCAN_BINS * COLSCAN_ROW_LANES)
+radix_colscan_kernel(uint32_t* __restrict__ hist, uint32_t nb, uint32_t bins, uint32_t* __restrict__ totals) {
+    __shared__ uint32_t part[COLSCAN_ROW_LANES][COLSCAN_BINS];
+    const uint32_t bl = threadIdx.x % COLSCAN_BINS, rl = threadIdx.x / COLSCAN_BINS;
+    const uint32_t d = blockIdx.x * COLSCAN_BINS + bl;        // (bins is a multiple of COLSCAN_BINS: every thread owns a column)
+    uint32_t carry = 0;
+    for (uint32_t row0 = 0; row0 < nb; row0 += COLSCAN_SWEEP_ROWS) {
+        const uint32_t rows = min(nb - row0, (uint32_t)COLSCAN_SWEEP_ROWS);
+        const uint32_t run = (rows + COLSCAN_ROW_LANES - 1) / COLSCAN_ROW_LANES;      // rows a row lane owns in this sweep
+        const uint32_t first = row0 + rl * run, end = min(first + run, row0 + rows);   // (first >= end: a row lane behind the last row)
+        uint32_t v[COLSCAN_RUN];
+#pragma unroll
+        for (int k = 0; k < COLSCAN_RUN; k++) {
+            const uint32_t r = first + (uint32_t)k;
+            const uint32_t x = hist[(size_t)(r < end ? r : row0) * bins + d];        // (unconditional loads: one run of requests, one wait)
+            v[k] = r < end ? x : 0u;
+        }
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < COLSCAN_RUN; k++) {
+            const uint32_t x = v[k];
+            v[k] = sum;                  // exclusive inside the run
+            sum += x;
+        }
+        part[rl][bl] = sum;
+        __syncthreads();
+        uint32_t before = carry, tot = 0;
+#pragma unroll
+        for (int j = 0; j < COLSCAN_ROW_LANES; j++) {
+            const uint32_t t = part[j][bl];
+            before += (uint32_t)j < rl ? t : 0u;
+            tot += t;
+        }
+#pragma unroll
+        for (int k = 0; k < COLSCAN_RUN; k++) {
+            const uint32_t r = first + (uint32_t)k;
+            if (r < end) hist[(size_t)r * bins + d] = before + v[k];
+        }
+        carry += tot;
+        __syncthreads();                 // every total read before the next sweep's are written
+    }
+    if (rl == 0) totals[d] = carry;
 }
 
 // One workgroup per digit: exclusive scan of that digit's per-workgroup counts, total to totals[d].
@@ -219,7 +280,8 @@ __device__ __forceinline__ void record_range(uint2* ranges_enc, uint32_t tile, b
 // payload[value] instead - the Gaussian's tile count at its place in the depth order (GeomState::key_a), gathered here, where
 // the id is in a register anyway, rather than by the two kernels that walk the order afterwards.  The same stores, no more LDS.
 // BUCKET (see radix_hist_kernel; never with REORDER): the digit is the key's bucket by ctl[0 .. 1], and workgroup 0 leaves every
-// bucket's first position in bucket_offs for the launch that sorts the buckets.
+// bucket's first position in bucket_offs for the launch that sorts the buckets.  `hist` is row-major (the workgroup's row, scanned
+// by radix_colscan_kernel) and keys_out is the B side's run of 2n words, which receives (key, id) PAIRS; vals_out is not used.
 template <int BITS, int ITEMS, bool REORDER, bool RANGES, bool COUNTS = false, bool BUCKET = false>
 __global__ void __launch_bounds__(SORT_THREADS)
 radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
@@ -269,6 +331,20 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
         const size_t i = wbase + (size_t)k * 64 + lane;
         key[k] = i < n ? keys_in[i] : 0xFFFFFFFFu;
         if constexpr (VAL_FIRST) val[k] = (vals_in && i < n) ? vals_in[i] : (uint32_t)i;
+    }
+    // BUCKET: the matrix is row-major (radix_hist_kernel) - a thread's BPT bins are BPT consecutive words of the workgroup's row,
+    // requested here with 16-byte loads behind the keys and needed only in the offset phase (digit-major they were BPT single
+    // words 4 nb bytes apart, requested there)
+    uint32_t hrow[BUCKET ? BPT : 1];
+    (void)hrow;
+    if constexpr (BUCKET) {
+        static_assert(BPT % 4 == 0, "whole 16-byte loads per thread");
+        const uint4* const row = reinterpret_cast<const uint4*>(hist + (size_t)blockIdx.x * BINS + (size_t)threadIdx.x * BPT);
+#pragma unroll
+        for (int q = 0; q < BPT / 4; q++) {
+            const uint4 t = row[q];
+            hrow[4 * q] = t.x; hrow[4 * q + 1] = t.y; hrow[4 * q + 2] = t.z; hrow[4 * q + 3] = t.w;
+        }
     }
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
@@ -322,7 +398,7 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
         for (int q = 0; q < BPT; q++) {
             const uint32_t d = threadIdx.x * BPT + q;
             if (BINS < SORT_THREADS && d >= (uint32_t)BINS) break;
-            const uint32_t g = digit_base + hist[(size_t)d * nb + blockIdx.x];
+            const uint32_t g = digit_base + (BUCKET ? hrow[BUCKET ? q : 0] : hist[(size_t)d * nb + blockIdx.x]);
             if (BUCKET && blockIdx.x == 0) bucket_offs[d] = digit_base;
             if (REORDER) { gbase[d] = g; lstart[d] = local_base; }
             uint32_t r2 = REORDER ? local_base : g;
@@ -402,6 +478,10 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
                 if constexpr (COUNTS) {
                     keys_out[pos] = pay[k];
                     vals_out[pos] = val[k];
+                } else if constexpr (BUCKET) {
+                    // the B side as pairs: keys_out is its 2P-word run, ONE 8-byte store an item where two 4-byte stores to unrelated
+                    // lines went out (a workgroup's 2,048 keys fall into hundreds of buckets: no run of neighbours to merge)
+                    reinterpret_cast<uint2*>(keys_out)[pos] = make_uint2(key[k], (uint32_t)i);
                 } else {
                     keys_out[pos] = key[k];
                     vals_out[pos] = vals_in ? vals_in[i] : (uint32_t)i;
@@ -749,8 +829,9 @@ bool small_sort_usable() {
 }
 
 // =====================================================================================================
-// Depth sort by buckets, second half (common.h: depth sort by buckets): behind the bucket pass - histogram, row scan and stable
-// scatter on the bucket index, into the B side - every bucket is one contiguous run of (key, id) pairs in id order, and ONE launch
+// Depth sort by buckets, second half (common.h: depth sort by buckets): behind the bucket pass - histogram, column scan and stable
+// scatter on the bucket index, into the B side - every bucket is one contiguous run of (key, id) pairs in id order (pair_b: one
+// uint2 an item, stored and loaded 8 bytes at a time), and ONE launch
 // sorts them all, one workgroup per bucket, with the passes of small_sort_kernel (ballot ranking, wave-ordered LDS counters, three
 // barriers a pass, stable).  Inside a bucket the order of two keys is the order of the low s bits of key - kmin (the bits above
 // are the bucket index), so a workgroup sorts those, and of those only the ones in which its keys differ: two 8-bit passes where
@@ -801,29 +882,35 @@ __device__ __forceinline__ uint32_t bucket_block_or(uint32_t v, uint32_t* red) {
     return r;
 }
 
-// A bucket above the capacity: streaming LSD passes B -> A -> B -> ... over its own index range, an odd number of them
-__device__ __forceinline__ void depth_bucket_stream_sort(BucketSortLds& L, uint32_t* key_b, uint32_t* val_b, uint32_t* key_a, uint32_t* val_a,
+// A bucket above the capacity: streaming LSD passes B -> A -> B -> ... over its own index range, an odd number of them.  The B side
+// holds the bucket as n pairs, pair_b[off .. off + n): the first pass reads them as pairs; from then on those 2n words are the
+// workgroup's private scratch, cut into a key half and an id half like the A side (sk / sv and dk / dv point at item 0 of the
+// bucket on either side), so the later passes are the ping-pong of two arrays they always were.
+__device__ __forceinline__ void depth_bucket_stream_sort(BucketSortLds& L, uint2* pair_b, uint32_t* key_a, uint32_t* val_a,
                                                       uint32_t off, uint32_t n, uint32_t kmin, uint32_t low, uint32_t rel0,
                                                       const uint32_t* __restrict__ payload) {
     constexpr int THREADS = DEPTH_BUCKET_THREADS, ITEMS = 8, NW = THREADS / 64;       // (chunks of eight items a thread: fewer registers than the in-LDS path holds)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     volatile uint32_t* vcnt = &L.cnt[w][0];
+    const uint2* const pairs = pair_b + off;
     uint32_t diff = 0;
-    for (uint32_t j = tid; j < n; j += THREADS) diff |= ((key_b[off + j] - kmin) & low) ^ rel0;
+    for (uint32_t j = tid; j < n; j += THREADS) diff |= ((pairs[j].x - kmin) & low) ^ rel0;
     diff = bucket_block_or(diff, L.red[0]);
     int passes = (32 - __clz((int)diff) + 7) / 8;
     if ((passes & 1) == 0) passes++;          // (a pass on bits in which no two keys differ is a stable copy)
     uint32_t* const gbase = L.key;            // [256] next position of every digit
-    uint32_t *sk = key_b, *sv = val_b, *dk = key_a, *dv = val_a;
+    uint32_t* const scratch = reinterpret_cast<uint32_t*>(pair_b + off);        // (2n words, 8-byte aligned whatever off and n are)
+    uint32_t *sk = scratch, *sv = scratch + n, *dk = key_a + off, *dv = val_a + off;
     for (int pass = 0; pass < passes; pass++) {
         const int shift = 8 * pass;
         const bool last = pass + 1 == passes;
+        const bool first = pass == 0;         // (the source is the pairs, not sk / sv)
         auto digit_of = [&](uint32_t kk) -> uint32_t { return shift < 32 ? (((kk - kmin) & low) >> shift) & 255u : 0u; };
         __syncthreads();
         if (tid < 256) gbase[tid] = 0;
         __syncthreads();
-        for (uint32_t j = tid; j < n; j += THREADS) atomicAdd(&gbase[digit_of(sk[off + j])], 1u);
+        for (uint32_t j = tid; j < n; j += THREADS) atomicAdd(&gbase[digit_of(first ? pairs[j].x : sk[j])], 1u);
         __syncthreads();
         {
             const uint32_t tot = tid < 256 ? gbase[tid] : 0u;
@@ -850,9 +937,9 @@ __device__ __forceinline__ void depth_bucket_stream_sort(BucketSortLds& L, uint3
 #pragma unroll
             for (int k = 0; k < ITEMS; k++) {
                 const uint32_t i = wbase + (uint32_t)(k * 64);
-                const uint32_t ii = off + (i < n ? i : 0u);
-                key[k] = sk[ii];
-                val[k] = sv[ii];
+                const uint32_t ii = i < n ? i : 0u;
+                if (first) { const uint2 p = pairs[ii]; key[k] = p.x; val[k] = p.y; }
+                else { key[k] = sk[ii]; val[k] = sv[ii]; }
             }
 #pragma unroll
             for (int k = 0; k < ITEMS; k++) {
@@ -875,7 +962,7 @@ __device__ __forceinline__ void depth_bucket_stream_sort(BucketSortLds& L, uint3
             for (int k = 0; k < ITEMS; k++) {
                 const uint32_t i = wbase + (uint32_t)(k * 64);
                 if (i < n) {
-                    const uint32_t pos = off + L.cnt[w][digit_of(key[k])] + rank[k];
+                    const uint32_t pos = L.cnt[w][digit_of(key[k])] + rank[k];
                     dk[pos] = last ? payload[val[k]] : key[k];
                     dv[pos] = val[k];
                 }
@@ -892,21 +979,24 @@ __device__ __forceinline__ void depth_bucket_stream_sort(BucketSortLds& L, uint3
     }
 }
 
-// (the four arrays are read AND written by the streaming passes: no __restrict__, no const)
+// (the three arrays are read AND written by the streaming passes: no __restrict__, no const)
 __global__ void __launch_bounds__(DEPTH_BUCKET_THREADS, 4)      // (four waves per SIMD: two workgroups per CU)
-depth_bucket_sort_kernel(uint32_t* key_b, uint32_t* val_b, uint32_t* key_a, uint32_t* val_a, uint32_t bins,
+depth_bucket_sort_kernel(uint2* pair_b, uint32_t* key_a, uint32_t* val_a, uint32_t bins,
                          const uint32_t* __restrict__ totals, const uint32_t* __restrict__ offs, uint32_t* __restrict__ ctl,
                          const uint32_t* __restrict__ payload, uint32_t* __restrict__ stats_host) {
     extern __shared__ __attribute__((aligned(16))) char bucket_sort_smem[];
     BucketSortLds& L = *reinterpret_cast<BucketSortLds*>(bucket_sort_smem);
     constexpr int THREADS = DEPTH_BUCKET_THREADS, ITEMS = DEPTH_BUCKET_ITEMS, NW = THREADS / 64;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const uint32_t b = blockIdx.x;
+    // The buckets are taken from the FAR end: the keys are float bits, a logarithmic scale, so a far bucket spans more depth and holds
+    // more keys (c3: about 980 in the nearest octave's, 3,900 in the farthest's), and the 576 non-empty workgroups run on 512 slots - in
+    // index order the longest sorts started last, behind everything else (0.0621 -> 0.0584 ms for the stage at c3)
+    const uint32_t b = blockIdx.x < bins - 1u ? bins - 2u - blockIdx.x : blockIdx.x;
     if (b >= bins - 1u) {
         // the culled bucket: ids in id order already, moved to the A side with their tile counts
         const uint32_t off = offs[bins - 1u], n = totals[bins - 1u];
         for (uint32_t j = (b - (bins - 1u)) * THREADS + tid; j < n; j += DEPTH_BUCKET_COPY_GROUPS * THREADS) {
-            const uint32_t id = val_b[off + j];
+            const uint32_t id = pair_b[off + j].y;
             val_a[off + j] = id;
             key_a[off + j] = payload[id];
         }
@@ -944,7 +1034,7 @@ depth_bucket_sort_kernel(uint32_t* key_b, uint32_t* val_b, uint32_t* key_a, uint
     const uint32_t kmin = ctl[0], bshift = ctl[1];
     const uint32_t low = (1u << bshift) - 1u;             // (the shift is 29 at most: depth_bucket_shift)
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const uint32_t rel0 = (key_b[off] - kmin) & low;
+    const uint32_t rel0 = (pair_b[off].x - kmin) & low;
     volatile uint32_t* vcnt = &L.cnt[w][0];
 
     if (n <= (uint32_t)DEPTH_BUCKET_CAP) {
@@ -958,9 +1048,9 @@ depth_bucket_sort_kernel(uint32_t* key_b, uint32_t* val_b, uint32_t* key_a, uint
             const uint32_t i = wbase + (uint32_t)(k * 64);
             const bool mine = k < steps && i < n;
             const uint32_t ii = mine ? off + i : off;         // (unconditional: one run of requests)
-            const uint32_t kk = key_b[ii];
-            val[k] = val_b[ii];
-            key[k] = mine ? (kk - kmin) & low : rel0;
+            const uint2 p = pair_b[ii];                       // one 8-byte load an item
+            val[k] = p.y;
+            key[k] = mine ? (p.x - kmin) & low : rel0;
             diff |= key[k] ^ rel0;
         }
         diff = bucket_block_or(diff, L.red[0]);
@@ -1055,7 +1145,7 @@ depth_bucket_sort_kernel(uint32_t* key_b, uint32_t* val_b, uint32_t* key_a, uint
         return;
     }
 
-    depth_bucket_stream_sort(L, key_b, val_b, key_a, val_a, off, n, kmin, low, rel0, payload);
+    depth_bucket_stream_sort(L, pair_b, key_a, val_a, off, n, kmin, low, rel0, payload);
 }
 
 bool depth_bucket_sort_usable() {
@@ -1187,9 +1277,11 @@ hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* va
     }
     // the last pass hands the tile counts on in the new order instead of the keys, where the caller can take them
     const uint32_t* const payload = (counts_in_a && sums) ? sums->tiles_touched : nullptr;
-    if (buckets && payload && tj && tj->partial && n < (1ull << 31) && depth_bucket_sort_usable()) {
-        // four launches: the bucket pass into the B side (histogram - with the totals job and the key range -, row scan, stable
-        // scatter), then every bucket sorted inside LDS into the A side (depth_bucket_sort_kernel)
+    // (the B side as one run of 2n words, 8-byte aligned: GeomState::carve)
+    const bool b_is_one_run = val_b == key_b + n && (reinterpret_cast<uintptr_t>(key_b) & 7u) == 0;
+    if (buckets && payload && tj && tj->partial && n < (1ull << 31) && b_is_one_run && depth_bucket_sort_usable()) {
+        // four launches: the bucket pass into the B side (histogram - with the totals job and the key range -, column scan, stable
+        // scatter of pairs), then every bucket sorted inside LDS into the A side (depth_bucket_sort_kernel)
         const uint32_t count = depth_bucket_count(n);
         const uint32_t nb = (uint32_t)((n + SORT_THREADS * SORT_ITEMS - 1) / (SORT_THREADS * SORT_ITEMS));
         const bool wide = depth_bucket_bits(n) == DEPTH_BUCKET_BITS_WIDE;
@@ -1206,7 +1298,8 @@ hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* va
                                nb, hist, *tj, none, count, ctl);
         hipError_t rc = hipSuccess;
         if (tj->ready) rc = hipEventRecord(tj->ready, s);        // the totals are final behind this launch
-        hipLaunchKernelGGL(radix_rowscan_kernel, dim3(bins), dim3(256), 0, s, hist, nb, totals);
+        hipLaunchKernelGGL(radix_colscan_kernel, dim3(bins / COLSCAN_BINS), dim3(COLSCAN_BINS * COLSCAN_ROW_LANES), 0, s, hist, nb, bins,
+                           totals);
         if (wide)
             hipLaunchKernelGGL((radix_scatter_kernel<DEPTH_BUCKET_BITS_WIDE, SORT_ITEMS, false, false, false, true>), dim3(nb),
                                dim3(SORT_THREADS), 0, s, keys, none, key_b, val_b, n, 0, nb, hist, totals, (uint2*)nullptr, none, none,
@@ -1216,7 +1309,8 @@ hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* va
                                dim3(SORT_THREADS), 0, s, keys, none, key_b, val_b, n, 0, nb, hist, totals, (uint2*)nullptr, none, none,
                                (const uint32_t*)ctl, offs);
         hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(bins - 1u + DEPTH_BUCKET_COPY_GROUPS), dim3(DEPTH_BUCKET_THREADS),
-                           sizeof(BucketSortLds), s, key_b, val_b, key_a, val_a, bins, (const uint32_t*)totals, (const uint32_t*)offs, ctl,
+                           sizeof(BucketSortLds), s, reinterpret_cast<uint2*>(key_b), key_a, val_a, bins, (const uint32_t*)totals,
+                           (const uint32_t*)offs, ctl,
                            payload, stats_host);
         *counts_in_a = true;
         if (info) *info = DepthSortInfo{F3DGS_DEPTH_SORT_BUCKETS, count, (uint32_t)DEPTH_BUCKET_CAP};

@@ -118,8 +118,9 @@ constexpr int DEPTH_BUCKET_MIN_COUNT = 16;
 constexpr int DEPTH_BUCKET_COPY_GROUPS = 128;         // workgroups that move the culled bucket (no sort: the stable pass left it in id order)
 // option depth_sort_buckets = -1: the bucket path is taken for DEPTH_BUCKET_AUTO_ABOVE < P <= DEPTH_BUCKET_AUTO_UPTO, where it was
 // measured faster than the multi-launch LSD passes (profiles/depth_bucket_sort.md): from the first size beyond the one-launch sort
-// (16,385: 0.038 against 0.065 ms) to the last size of the 10-bit pass (1.25M: 0.092 against 0.108); the 11-bit pass loses at 2M
-// (0.146 against 0.142), and at 5M the buckets of an even spread no longer fit the capacity
+// (16,385: 0.038 against 0.065 ms) to the last size of the 10-bit pass (1.25M: 0.092 against 0.108); the 11-bit pass lost at 2M
+// (0.146 against 0.142) when the thresholds were set - with the row-major matrix and the pair stores it reads 0.103, the default
+// beyond 1.25M has not been revisited -, and at 5M the buckets of an even spread no longer fit the capacity
 constexpr size_t DEPTH_BUCKET_AUTO_ABOVE = SMALL_SORT_MAX;
 constexpr size_t DEPTH_BUCKET_AUTO_UPTO = DEPTH_BUCKET_WIDE_ABOVE;
 static_assert(DEPTH_BUCKET_CAP <= DEPTH_BUCKET_THREADS * DEPTH_BUCKET_ITEMS && DEPTH_BUCKET_CAP % 64 == 0, "a bucket in LDS: whole waves, within the threads' items");
@@ -151,7 +152,15 @@ static_assert(depth_bucket_shift(0, 14, 16) == 0 && depth_bucket_shift(0, 15, 16
 static_assert(depth_bucket_shift(0x40000000u, 0x41200000u, 1024) == 15, "z in 2 .. 10 over 1024 bins: 576 buckets of 2^15 keys");
 static_assert(depth_bucket_shift(0u, 0xFFFFFFFEu, 16) == 29 && (0xFFFFFFFEu >> 29) <= 14u, "the widest range stays below 32");
 
-constexpr int DEPTH_BUCKET_CTL_WORDS = 64;            // [0] kmin, [1] shift, [2] largest bucket, [3] buckets above the capacity
+// the bucket pass's column scan (radix_colscan_kernel): a workgroup owns COLSCAN_BINS bins - one 64-byte sector of every row -,
+// its threads are COLSCAN_BINS bin lanes x COLSCAN_ROW_LANES row lanes, a row lane owns up to COLSCAN_RUN consecutive rows a sweep
+constexpr int COLSCAN_BINS = 16;
+constexpr int COLSCAN_ROW_LANES = 16;
+constexpr int COLSCAN_RUN = 32;
+constexpr int COLSCAN_SWEEP_ROWS = COLSCAN_ROW_LANES * COLSCAN_RUN;
+static_assert(COLSCAN_SWEEP_ROWS == 512 && (size_t)COLSCAN_SWEEP_ROWS * SORT_CHUNK >= 1000000,
+              "1M keys (489 rows) in one sweep; tests/depth_bucket_layout_cases.py restates the 512");
+constexpr int DEPTH_BUCKET_CTL_WORDS = 64;           // [0] kmin, [1] shift, [2] largest bucket, [3] buckets above the capacity
 static_assert(DEPTH_BUCKET_BITS_WIDE <= DEPTH_RADIX_BITS, "GeomState::hist is sized for the widest depth pass");
 
 inline size_t sort_blocks(size_t n) { return (n + SORT_CHUNK - 1) / SORT_CHUNK; }
@@ -168,11 +177,13 @@ struct GeomState {
                               //     keys (nobody reads them) but tiles_touched in depth order - key_a[i] = tiles_touched[val_a[i]], stored by
                               //     the sort's last scatter, which holds the id anyway - for the offset sums and the emit kernel to read in
                               //     a row; the one-workgroup sort and the look-back flavour leave keys (or nothing) there
-    uint32_t* key_b;
     uint32_t* val_a;
-    uint32_t* val_b;
+    uint32_t* key_b;          // 2P  the B side, ONE 8-byte-aligned run: the LSD passes use its halves (key_b, val_b = key_b + P) as before,
+    uint32_t* val_b;          //     the bucket pass stores P (key, id) pairs there, one 8-byte store an item (binning.hip)
     uint32_t* hist;           // DEPTH_RADIX_BINS * sort_blocks(P) + DEPTH_RADIX_BINS (histogram matrix and totals of a pass), and behind
-                              //     them, for the bucket pass, the buckets' offsets and DEPTH_BUCKET_CTL_WORDS control words
+                              //     them, for the bucket pass, the buckets' offsets and DEPTH_BUCKET_CTL_WORDS control words.  The
+                              //     matrix is digit-major for the LSD passes, hist[d * blocks + block], and row-major for the bucket
+                              //     pass, hist[block * bins + d]: a workgroup's counts are one contiguous row of 4 or 8 KB
     uint32_t* scan_tmp;       // scan_blocks(P) + 8      list entries of every chunk of SCAN_CHUNK Gaussians in depth order
     uint32_t* scan_sub;       // 64 x scan_blocks(P)     list entries of every run of 64 Gaussians in depth order
     uint32_t* ref_partial;    // per preprocess workgroup: bounding-rectangle tile counts, then list-entry counts, then 1 if a visible Gaussian of the workgroup has a long axis,
@@ -200,9 +211,9 @@ struct GeomState {
         g.tiles_touched = c.take<uint32_t>(P);
         g.depth_key = c.take<uint32_t>(P);
         g.key_a = c.take<uint32_t>(P);
-        g.key_b = c.take<uint32_t>(P);
         g.val_a = c.take<uint32_t>(P);
-        g.val_b = c.take<uint32_t>(P);
+        g.key_b = c.take<uint32_t>(2 * P);      // the B side: one run of 2P words (the bucket pass stores P pairs there)
+        g.val_b = g.key_b ? g.key_b + P : nullptr;
         g.hist = c.take<uint32_t>(DEPTH_RADIX_BINS * sort_blocks(P) + 2 * DEPTH_RADIX_BINS + DEPTH_BUCKET_CTL_WORDS);
         g.scan_tmp = c.take<uint32_t>(scan_blocks(P) + 8);
         g.scan_sub = c.take<uint32_t>(64 * scan_blocks(P));
