@@ -355,7 +355,8 @@ radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
         uint32_t p_lo = (uint32_t)vm, p_hi = (uint32_t)(vm >> 32);
 #pragma unroll
         for (int b = 0; b < BITS; b++) {
-            // x: all ones where the lane's digit has bit b; a peer's bit equals it: peers &= ~(ballot ^ x) = ~ballot ^ x
+            // (wave_digit_rank, wg_sort.h, written out: through the helper the 4- and 6-bit instantiations come out one and two
+            // instructions longer, profiles/wg_sort_core.md 2)
             const uint32_t x = 0u - ((d >> b) & 1u);
             const unsigned long long nm = ~__ballot(x != 0u);
             p_lo &= (uint32_t)nm ^ x;
@@ -534,18 +535,7 @@ onesweep_pass_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __res
         const size_t i = wbase + (size_t)k * 64 + lane;
         const bool valid = i < n;
         key[k] = valid ? keys_in[i] : 0xFFFFFFFFu;
-        const uint32_t d = (key[k] >> shift) & (BINS - 1);
-        unsigned long long peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const bool bit = (d >> b) & 1;
-            const unsigned long long m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        const uint32_t before = __popcll(peers & lt_mask);
-        const uint32_t old = vcnt[w * BINS + d];
-        if (valid && before == 0) vcnt[w * BINS + d] = old + (uint32_t)__popcll(peers);
-        rank[k] = old + before;
+        rank[k] = wave_digit_rank(valid, (key[k] >> shift) & (BINS - 1), 8, &vcnt[w * BINS], lt_mask);
     }
     __syncthreads();
     {   // thread d owns digit d
@@ -662,21 +652,17 @@ void launch_offset_sums(const uint32_t* in, const uint32_t* gather, size_t n, ui
 // =====================================================================================================
 // Small problems (up to SMALL_SORT_MAX pairs: config c1, early training, inference on small scenes): the WHOLE stable sort in
 // one launch of one workgroup, resident in LDS.  A multi-launch pass costs ~20 us of dependent launches whatever the size (c1:
-// nine launches = 0.060 ms for 10,000 depth keys, three = 0.024 ms for 16,076 instances); here every 8-bit pass is: rank the
-// thread's 16 items per wave (the ballot match of radix_scatter_kernel, wave-ordered LDS counters), turn the 16 x 256 counters
-// into offsets, scatter the pairs into the LDS image, read them back in the new order - three barriers, no global round trip.
+// nine launches = 0.060 ms for 10,000 depth keys, three = 0.024 ms for 16,076 instances); here every 8-bit pass (lds_radix_pass,
+// wg_sort.h) is: rank the thread's 16 items per wave (the ballot match of radix_scatter_kernel, wave-ordered LDS counters), turn the
+// 16 x 256 counters into offsets, scatter the pairs into the LDS image, read them back in the new order - three barriers, no global
+// round trip.
 // The pairs live in registers between passes; the LDS image is written out once at the end (with the tile ranges, RANGES).
 // (A first version of this idea - round 4, removed - ping-ponged the pairs through global memory behind fences: slower than the
 // launches it replaced.)
 // (SMALL_SORT_MAX = 16384: common.h)
 constexpr int SMALL_SORT_THREADS = 1024;
 constexpr int SMALL_SORT_ITEMS = SMALL_SORT_MAX / SMALL_SORT_THREADS;     // 16
-struct SmallSortLds {
-    uint32_t key[SMALL_SORT_MAX];
-    uint32_t val[SMALL_SORT_MAX];
-    uint32_t cnt[SMALL_SORT_THREADS / 64][256];
-    uint32_t wsum[4];
-};
+using SmallSortLds = SortLds<SMALL_SORT_THREADS, SMALL_SORT_MAX>;
 template <bool RANGES>
 __global__ void __launch_bounds__(SMALL_SORT_THREADS)
 small_sort_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t* __restrict__ keys_out,
@@ -684,14 +670,11 @@ small_sort_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restri
                   const uint32_t* __restrict__ n_dev, OffsetSumsJob os) {
     extern __shared__ __attribute__((aligned(16))) char small_sort_smem[];
     SmallSortLds& L = *reinterpret_cast<SmallSortLds*>(small_sort_smem);
-    constexpr int ITEMS = SMALL_SORT_ITEMS, NW = SMALL_SORT_THREADS / 64;
+    constexpr int ITEMS = SMALL_SORT_ITEMS;
     if (n_dev) { const uint32_t nd = *n_dev; n = nd <= n ? nd : 0u; }       // (sync-free forward) n is a capacity, the item count is the device's word; a frame that does not fit is void
     if (tj.partial) run_totals_job<SMALL_SORT_THREADS>(tj);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    volatile uint32_t* vcnt = &L.cnt[w][0];
-    // item order: wave w owns [64 steps w, 64 steps (w + 1)), visited in `steps` <= 16 steps of 64 consecutive items (lane = item
-    // within the step): the items are spread evenly over the sixteen waves, the unused steps of a small problem are skipped
+    // item order: lds_radix_pass's (wg_sort.h), in `steps` <= 16 steps
     const int steps = (int)((n + SMALL_SORT_THREADS - 1) / SMALL_SORT_THREADS);
     const uint32_t wbase = (uint32_t)(w * steps * 64 + lane);
     uint32_t key[ITEMS], val[ITEMS], rank[ITEMS];
@@ -702,77 +685,8 @@ small_sort_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restri
         key[k] = mine ? keys_in[i] : 0xFFFFFFFFu;
         val[k] = (vals_in && mine) ? vals_in[i] : i;
     }
-    for (int pass = 0; pass < passes; pass++) {
-        const int shift = 8 * pass;
-        for (int d = tid; d < NW * 256; d += SMALL_SORT_THREADS) (&L.cnt[0][0])[d] = 0;
-        __syncthreads();       // counters cleared; the previous pass's read-back is complete
-#pragma unroll
-        for (int k = 0; k < ITEMS; k++) {
-            if (k >= steps) break;
-            const uint32_t i = wbase + (uint32_t)(k * 64);
-            const bool valid = i < n;
-            const uint32_t d = (key[k] >> shift) & 255u;
-            const unsigned long long vm = __ballot(valid);
-            uint32_t p_lo = (uint32_t)vm, p_hi = (uint32_t)(vm >> 32);
-#pragma unroll
-            for (int b = 0; b < 8; b++) {
-                const uint32_t x = 0u - ((d >> b) & 1u);
-                const unsigned long long nm = ~__ballot(x != 0u);
-                p_lo &= (uint32_t)nm ^ x;
-                p_hi &= (uint32_t)(nm >> 32) ^ x;
-            }
-            const unsigned long long peers = ((unsigned long long)p_hi << 32) | p_lo;
-            const uint32_t before = __popcll(peers & lt_mask);
-            const uint32_t old = vcnt[d];
-            if (valid && before == 0) vcnt[d] = old + (uint32_t)__popcll(peers);
-            rank[k] = old + before;
-        }
-        __syncthreads();
-        // digit d = tid (first 256 threads): total over the waves, exclusive scan over the digits, then per-wave offsets
-        {
-            uint32_t tot = 0;
-            if (tid < 256) {
-#pragma unroll
-                for (int ww = 0; ww < NW; ww++) tot += L.cnt[ww][tid];
-            }
-            uint32_t inc = tot;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t v = (uint32_t)__shfl_up((int)inc, d, 64);
-                if (lane >= d) inc += v;
-            }
-            if (tid < 256 && lane == 63) L.wsum[w] = inc;
-            __syncthreads();
-            if (tid < 256) {
-                uint32_t base = inc - tot;
-                for (int ww = 0; ww < w; ww++) base += L.wsum[ww];
-#pragma unroll
-                for (int ww = 0; ww < NW; ww++) {
-                    const uint32_t c = L.cnt[ww][tid];
-                    L.cnt[ww][tid] = base;
-                    base += c;
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < ITEMS; k++) {
-            const uint32_t i = wbase + (uint32_t)(k * 64);
-            if (k < steps && i < n) {
-                const uint32_t pos = L.cnt[w][(key[k] >> shift) & 255u] + rank[k];
-                L.key[pos] = key[k];
-                L.val[pos] = val[k];
-            }
-        }
-        __syncthreads();
-        if (pass + 1 < passes) {
-#pragma unroll
-            for (int k = 0; k < ITEMS; k++) {
-                const uint32_t i = wbase + (uint32_t)(k * 64);
-                if (k < steps && i < n) { key[k] = L.key[i]; val[k] = L.val[i]; }
-            }
-        }
-    }
+    for (int pass = 0; pass < passes; pass++)
+        lds_radix_pass<SMALL_SORT_THREADS, ITEMS>(L, key, val, rank, steps, n, 8 * pass, pass + 1 >= passes);
 #pragma unroll
     for (int k = 0; k < ITEMS; k++) {
         const uint32_t j = (uint32_t)(k * SMALL_SORT_THREADS + tid);
@@ -812,28 +726,30 @@ small_sort_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restri
 
 __global__ void __launch_bounds__(256) totals_kernel(TotalsJob tj) { run_totals_job<256>(tj); }
 
-// The LDS image is 144 KB: above the default limit, raised once per device (refused: the multi-launch passes take over).
-template <bool RANGES>
-bool small_sort_usable() {
+// A kernel whose dynamic LDS is above the default limit: raised once per device (refused: the caller's other path takes over).
+template <auto KERNEL>
+bool raise_lds_limit(size_t bytes) {
     constexpr int MAX_DEV = 64;
     static std::atomic<int> state[MAX_DEV];      // 0: not asked yet, 1: usable, -1: refused (the ABI is re-entrant across threads)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return false;
     if (state[dev].load(std::memory_order_acquire) == 0) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&small_sort_kernel<RANGES>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallSortLds));
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) (void)hipGetLastError();
         state[dev].store(e == hipSuccess ? 1 : -1, std::memory_order_release);
     }
     return state[dev].load(std::memory_order_acquire) > 0;
 }
+// The one-launch sort's LDS image is 144 KB (refused: the multi-launch passes take over).
+template <bool RANGES>
+bool small_sort_usable() { return raise_lds_limit<&small_sort_kernel<RANGES>>(sizeof(SmallSortLds)); }
 
 // =====================================================================================================
 // Depth sort by buckets, second half (common.h: depth sort by buckets): behind the bucket pass - histogram, column scan and stable
 // scatter on the bucket index, into the B side - every bucket is one contiguous run of (key, id) pairs in id order (pair_b: one
 // uint2 an item, stored and loaded 8 bytes at a time), and ONE launch
-// sorts them all, one workgroup per bucket, with the passes of small_sort_kernel (ballot ranking, wave-ordered LDS counters, three
-// barriers a pass, stable).  Inside a bucket the order of two keys is the order of the low s bits of key - kmin (the bits above
+// sorts them all, one workgroup per bucket, with the passes of small_sort_kernel (lds_radix_pass, wg_sort.h: ballot ranking,
+// wave-ordered LDS counters, three barriers a pass, stable).  Inside a bucket the order of two keys is the order of the low s bits of key - kmin (the bits above
 // are the bucket index), so a workgroup sorts those, and of those only the ones in which its keys differ: two 8-bit passes where
 // the LSD sort of whole keys takes four.  The ids go to val_a and, in their place beside them in key_a, the tile counts
 // payload[id] - what the LSD sort's last scatter hands on (COUNTS).
@@ -841,33 +757,11 @@ bool small_sort_usable() {
 // workgroups of their own.  A bucket above DEPTH_BUCKET_CAP pairs (every Gaussian at one depth, say) owns the same index range on
 // both sides; its workgroup sorts it alone, in streaming LSD passes from one side to the other: slow, correct for any input, and
 // no workgroup ever waits for another.
-struct BucketSortLds {
-    uint32_t key[DEPTH_BUCKET_CAP];
-    uint32_t val[DEPTH_BUCKET_CAP];
-    uint32_t cnt[DEPTH_BUCKET_THREADS / 64][256];
-    uint32_t wsum[4];
+struct BucketSortLds : SortLds<DEPTH_BUCKET_THREADS, DEPTH_BUCKET_CAP> {
     uint32_t red[2][DEPTH_BUCKET_THREADS / 64];
 };
 static_assert(2 * sizeof(BucketSortLds) <= 160 * 1024, "two workgroups per CU");
 static_assert(DEPTH_BUCKET_CAP >= 512, "the streaming passes keep their digit offsets in the key image");
-
-// rank of an item among the items of its digit that the wave has seen so far in this pass (radix_scatter_kernel's ballot match)
-__device__ __forceinline__ uint32_t wave_digit_rank(uint32_t d, bool valid, volatile uint32_t* vcnt, unsigned long long lt_mask) {
-    const unsigned long long vm = __ballot(valid);
-    uint32_t p_lo = (uint32_t)vm, p_hi = (uint32_t)(vm >> 32);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        const uint32_t x = 0u - ((d >> b) & 1u);
-        const unsigned long long nm = ~__ballot(x != 0u);
-        p_lo &= (uint32_t)nm ^ x;
-        p_hi &= (uint32_t)(nm >> 32) ^ x;
-    }
-    const unsigned long long peers = ((unsigned long long)p_hi << 32) | p_lo;
-    const uint32_t before = __popcll(peers & lt_mask);
-    const uint32_t old = vcnt[d];
-    if (valid && before == 0) vcnt[d] = old + (uint32_t)__popcll(peers);
-    return old + before;
-}
 
 // OR of v over the workgroup's threads (all of them call), in every thread; red: one word per wave
 __device__ __forceinline__ uint32_t bucket_block_or(uint32_t v, uint32_t* red) {
@@ -912,22 +806,7 @@ __device__ __forceinline__ void depth_bucket_stream_sort(BucketSortLds& L, uint2
         __syncthreads();
         for (uint32_t j = tid; j < n; j += THREADS) atomicAdd(&gbase[digit_of(first ? pairs[j].x : sk[j])], 1u);
         __syncthreads();
-        {
-            const uint32_t tot = tid < 256 ? gbase[tid] : 0u;
-            uint32_t inc = tot;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t v = (uint32_t)__shfl_up((int)inc, d, 64);
-                if (lane >= d) inc += v;
-            }
-            if (tid < 256 && lane == 63) L.wsum[w] = inc;
-            __syncthreads();
-            if (tid < 256) {
-                uint32_t base = inc - tot;
-                for (int ww = 0; ww < w; ww++) base += L.wsum[ww];
-                gbase[tid] = base;
-            }
-        }
+        digit_offsets(gbase, L.wsum);
         for (uint32_t c0 = 0; c0 < n; c0 += THREADS * ITEMS) {
             // chunk of THREADS x ITEMS items in order: wave w owns 64 ITEMS consecutive ones
             for (int d = tid; d < NW * 256; d += THREADS) (&L.cnt[0][0])[d] = 0;
@@ -944,7 +823,7 @@ __device__ __forceinline__ void depth_bucket_stream_sort(BucketSortLds& L, uint2
 #pragma unroll
             for (int k = 0; k < ITEMS; k++) {
                 const uint32_t i = wbase + (uint32_t)(k * 64);
-                rank[k] = wave_digit_rank(digit_of(key[k]), i < n, vcnt, lt_mask);
+                rank[k] = wave_digit_rank(i < n, digit_of(key[k]), 8, vcnt, lt_mask);
             }
             __syncthreads();
             if (tid < 256) {
@@ -1033,12 +912,10 @@ depth_bucket_sort_kernel(uint2* pair_b, uint32_t* key_a, uint32_t* val_a, uint32
     const uint32_t off = offs[b];
     const uint32_t kmin = ctl[0], bshift = ctl[1];
     const uint32_t low = (1u << bshift) - 1u;             // (the shift is 29 at most: depth_bucket_shift)
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const uint32_t rel0 = (pair_b[off].x - kmin) & low;
-    volatile uint32_t* vcnt = &L.cnt[w][0];
 
     if (n <= (uint32_t)DEPTH_BUCKET_CAP) {
-        // item order: wave w owns [64 steps w, 64 steps (w + 1)), visited in `steps` steps of 64 consecutive items
+        // item order: lds_radix_pass's, in `steps` steps
         const int steps = (int)((n + THREADS - 1) / THREADS);
         const uint32_t wbase = (uint32_t)(w * steps * 64 + lane);
         uint32_t key[ITEMS], val[ITEMS], rank[ITEMS];
@@ -1067,61 +944,8 @@ depth_bucket_sort_kernel(uint2* pair_b, uint32_t* key_a, uint32_t* val_a, uint32
             }
             return;
         }
-        for (int pass = 0; pass < passes; pass++) {
-            const int shift = 8 * pass;
-            for (int d = tid; d < NW * 256; d += THREADS) (&L.cnt[0][0])[d] = 0;
-            __syncthreads();       // counters cleared; the previous pass's read-back is complete
-#pragma unroll
-            for (int k = 0; k < ITEMS; k++) {
-                if (k >= steps) break;
-                const uint32_t i = wbase + (uint32_t)(k * 64);
-                rank[k] = wave_digit_rank((key[k] >> shift) & 255u, i < n, vcnt, lt_mask);
-            }
-            __syncthreads();
-            {
-                uint32_t tot = 0;
-                if (tid < 256) {
-#pragma unroll
-                    for (int ww = 0; ww < NW; ww++) tot += L.cnt[ww][tid];
-                }
-                uint32_t inc = tot;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t v = (uint32_t)__shfl_up((int)inc, d, 64);
-                    if (lane >= d) inc += v;
-                }
-                if (tid < 256 && lane == 63) L.wsum[w] = inc;
-                __syncthreads();
-                if (tid < 256) {
-                    uint32_t base = inc - tot;
-                    for (int ww = 0; ww < w; ww++) base += L.wsum[ww];
-#pragma unroll
-                    for (int ww = 0; ww < NW; ww++) {
-                        const uint32_t c = L.cnt[ww][tid];
-                        L.cnt[ww][tid] = base;
-                        base += c;
-                    }
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < ITEMS; k++) {
-                const uint32_t i = wbase + (uint32_t)(k * 64);
-                if (k < steps && i < n) {
-                    const uint32_t pos = L.cnt[w][(key[k] >> shift) & 255u] + rank[k];
-                    L.key[pos] = key[k];
-                    L.val[pos] = val[k];
-                }
-            }
-            __syncthreads();
-            if (pass + 1 < passes) {
-#pragma unroll
-                for (int k = 0; k < ITEMS; k++) {
-                    const uint32_t i = wbase + (uint32_t)(k * 64);
-                    if (k < steps && i < n) { key[k] = L.key[i]; val[k] = L.val[i]; }
-                }
-            }
-        }
+        for (int pass = 0; pass < passes; pass++)
+            lds_radix_pass<THREADS, ITEMS>(L, key, val, rank, steps, n, 8 * pass, pass + 1 >= passes);
         // out in the new order, eight items of a thread at a time: their gathers all go out before the first store
         constexpr int HALF = ITEMS / 2;
         for (int h = 0; h < 2; h++) {
@@ -1148,19 +972,7 @@ depth_bucket_sort_kernel(uint2* pair_b, uint32_t* key_a, uint32_t* val_a, uint32
     depth_bucket_stream_sort(L, pair_b, key_a, val_a, off, n, kmin, low, rel0, payload);
 }
 
-bool depth_bucket_sort_usable() {
-    constexpr int MAX_DEV = 64;
-    static std::atomic<int> state[MAX_DEV];      // 0: not asked yet, 1: usable, -1: refused
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return false;
-    if (state[dev].load(std::memory_order_acquire) == 0) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&depth_bucket_sort_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BucketSortLds));
-        if (e != hipSuccess) (void)hipGetLastError();
-        state[dev].store(e == hipSuccess ? 1 : -1, std::memory_order_release);
-    }
-    return state[dev].load(std::memory_order_acquire) > 0;
-}
+bool depth_bucket_sort_usable() { return raise_lds_limit<&depth_bucket_sort_kernel>(sizeof(BucketSortLds)); }
 
 // ITEMS = keys per thread: 8 for the depth sort (2048-key workgroups: P = 1M gives 489 workgroups, about two per CU;
 // with 16 there are fewer workgroups than CUs and every pass is one latency chain: 0.116 -> 0.097 ms at c3), 16 for
@@ -1195,6 +1007,26 @@ static hipError_t radix_pass(const uint32_t* ki, const uint32_t* vi, uint32_t* k
     else
         hipLaunchKernelGGL((radix_scatter_kernel<BITS, ITEMS, (BITS <= 8), false>), dim3(nb), dim3(SORT_THREADS), 0, s, ki, vi, ko,
                            vo, n, shift, nb, hist, totals, (uint2*)nullptr, n_dev, no_payload, no_ctl, no_offs);
+    return rc;
+}
+
+// The bucket pass of the depth sort, BITS = log2 of its bins: histogram (with the totals job and the key range), column scan, stable
+// scatter of (key, id) pairs.  key_b / val_b: the B side, one run of 2n words (val_b = key_b + n) that receives the pairs; hist: the
+// row-major matrix of nb rows; totals, offs, ctl: where the caller carved them behind it.
+template <int BITS>
+static hipError_t launch_bucket_pass(const uint32_t* keys, uint32_t* key_b, uint32_t* val_b, size_t n, uint32_t nb, uint32_t* hist,
+                                     uint32_t* totals, uint32_t* offs, uint32_t* ctl, const TotalsJob& tj, uint32_t count,
+                                     hipStream_t s) {
+    constexpr uint32_t bins = 1u << BITS;
+    const uint32_t* const none = nullptr;
+    hipLaunchKernelGGL((radix_hist_kernel<BITS, SORT_ITEMS, true>), dim3(nb), dim3(SORT_THREADS), 0, s, keys, n, 0, nb, hist, tj, none,
+                       count, ctl);
+    hipError_t rc = hipSuccess;
+    if (tj.ready) rc = hipEventRecord(tj.ready, s);        // the totals are final behind this launch
+    hipLaunchKernelGGL(radix_colscan_kernel, dim3(bins / COLSCAN_BINS), dim3(COLSCAN_BINS * COLSCAN_ROW_LANES), 0, s, hist, nb, bins,
+                       totals);
+    hipLaunchKernelGGL((radix_scatter_kernel<BITS, SORT_ITEMS, false, false, false, true>), dim3(nb), dim3(SORT_THREADS), 0, s, keys,
+                       none, key_b, val_b, n, 0, nb, hist, totals, (uint2*)nullptr, none, none, (const uint32_t*)ctl, offs);
     return rc;
 }
 
@@ -1289,25 +1121,9 @@ hipError_t launch_depth_sort(const uint32_t* keys, uint32_t* key_a, uint32_t* va
         uint32_t* const totals = hist + (size_t)bins * nb;
         uint32_t* const offs = totals + bins;
         uint32_t* const ctl = offs + bins;
-        const uint32_t* const none = nullptr;
-        if (wide)
-            hipLaunchKernelGGL((radix_hist_kernel<DEPTH_BUCKET_BITS_WIDE, SORT_ITEMS, true>), dim3(nb), dim3(SORT_THREADS), 0, s, keys, n, 0,
-                               nb, hist, *tj, none, count, ctl);
-        else
-            hipLaunchKernelGGL((radix_hist_kernel<DEPTH_BUCKET_BITS, SORT_ITEMS, true>), dim3(nb), dim3(SORT_THREADS), 0, s, keys, n, 0,
-                               nb, hist, *tj, none, count, ctl);
-        hipError_t rc = hipSuccess;
-        if (tj->ready) rc = hipEventRecord(tj->ready, s);        // the totals are final behind this launch
-        hipLaunchKernelGGL(radix_colscan_kernel, dim3(bins / COLSCAN_BINS), dim3(COLSCAN_BINS * COLSCAN_ROW_LANES), 0, s, hist, nb, bins,
-                           totals);
-        if (wide)
-            hipLaunchKernelGGL((radix_scatter_kernel<DEPTH_BUCKET_BITS_WIDE, SORT_ITEMS, false, false, false, true>), dim3(nb),
-                               dim3(SORT_THREADS), 0, s, keys, none, key_b, val_b, n, 0, nb, hist, totals, (uint2*)nullptr, none, none,
-                               (const uint32_t*)ctl, offs);
-        else
-            hipLaunchKernelGGL((radix_scatter_kernel<DEPTH_BUCKET_BITS, SORT_ITEMS, false, false, false, true>), dim3(nb),
-                               dim3(SORT_THREADS), 0, s, keys, none, key_b, val_b, n, 0, nb, hist, totals, (uint2*)nullptr, none, none,
-                               (const uint32_t*)ctl, offs);
+        const hipError_t rc = wide
+            ? launch_bucket_pass<DEPTH_BUCKET_BITS_WIDE>(keys, key_b, val_b, n, nb, hist, totals, offs, ctl, *tj, count, s)
+            : launch_bucket_pass<DEPTH_BUCKET_BITS>(keys, key_b, val_b, n, nb, hist, totals, offs, ctl, *tj, count, s);
         hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(bins - 1u + DEPTH_BUCKET_COPY_GROUPS), dim3(DEPTH_BUCKET_THREADS),
                            sizeof(BucketSortLds), s, reinterpret_cast<uint2*>(key_b), key_a, val_a, bins, (const uint32_t*)totals,
                            (const uint32_t*)offs, ctl,

@@ -1,35 +1,11 @@
-// lookback.h - workgroup scan and decoupled look-back helpers shared by binning.hip and preprocess.hip.
+// lookback.h - the decoupled look-back protocol of the single-pass kernels (option sort_onesweep) of binning.hip and
+// preprocess.hip.  The workgroup scans that every kernel uses are in wg_sort.h.
 #pragma once
 
 #include "common.h"
+#include "wg_sort.h"
 
 namespace f3dgs {
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// Exclusive scan of one value per thread across a 256-thread workgroup. `sh` holds >= 8 words.
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* sh, uint32_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t inc = wave_incl_scan(v, lane);
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t s = sh[k];
-        if (k < w) base += s;
-    }
-    if (total) *total = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return base + inc - v;
-}
 
 // ---- decoupled look-back ------------------------------------------------------------------------------
 // A status word carries flag and value together (2 + 30 bits), so relaxed agent-scope loads and stores are

@@ -18,7 +18,7 @@ reference, at any P, in milliseconds.  Every case here checks
                    scalar oracle (tests/test_depth_order_cases_cpu.py); three of them also compared with the oracle's lists here
   other flavours   the same keys through the three 11-bit LSD passes and through the look-back passes
   LSD regimes      P = 16,385 / 200,000 (three 11-bit passes) and 200,001 (four 8-bit passes, the reordering scatter), tied keys
-  one launch       P = 1, 63, 64, 65, 16,383, 16,384; 16,384 equal keys; 16,384 culled
+  one launch       P = 1, 63, 64, 65, 1,024, 1,025, 15,360, 15,361, 16,383, 16,384; 16,384 equal keys; 16,384 culled
   large P          1,250,000 (buckets, 1,024 bins), 1,250,001 (passes by default; 2,048 bins under option 1 - the 11-bit bucket
                    pass), 1,250,001 with 60 % of the keys on two jittered planes (oversized buckets beside ordinary bins); there
                    also the tile sort over millions of entries, by numpy alone: sorted tile ids, ranges = run boundaries, every
@@ -141,8 +141,10 @@ def test_lsd_regime_edges_on_tied_keys(P, option):
 
 # ---- the one-launch sort ----------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("P", [1, 63, 64, 65, 16383, 16384])
+@pytest.mark.parametrize("P", [1, 63, 64, 65, 1024, 1025, 15360, 15361, 16383, 16384])
 def test_one_launch_sizes(P, option):
+    # (1,024 / 1,025 and 15,360 / 15,361: one step of the shared in-LDS pass against two, fifteen against sixteen; at every size the
+    # scalar oracle keeps more than half of the scene of seed 90 + P % 11 alive)
     option("tile_cull", 0)
     scene = _scene(P=P, C=0, seed=90 + P % 11, sh_degree=0, **doc.IMG, **doc.SMALL)
     if P == 1:
