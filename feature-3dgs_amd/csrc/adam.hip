@@ -197,8 +197,6 @@ reset_opacity_kernel(size_t n, float* __restrict__ raw, float* __restrict__ m, f
     if (v) v[i] = 0.0f;
 }
 
-}  // namespace
-
 void launch_adam_step_multi(int count, const f3dgs_adam_tensor* tensors, double b1, double b2, double eps, const uint8_t* row_mask,
                             size_t rows, hipStream_t s) {
     AdamTable tab;
@@ -272,4 +270,116 @@ void launch_adam_step(size_t n, float* p, const float* g, float* m, float* v, do
                        (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)(1.0 / sqrt(bc2)), (float)eps, row_mask, (uint32_t)(width ? width : 1));
 }
 
+// The checks f3dgs_adam_schedule and f3dgs_adam_step_multi_device share: both take the same table.
+int check_adam_device_table(const char* who, int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2,
+                            const void* consts, size_t* blocks_out) {
+    if (n_tensors < 0 || n_tensors > F3DGS_ADAM_MAX_TENSORS)
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: 0 .. %d tensors per call", who, F3DGS_ADAM_MAX_TENSORS);
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
+    *blocks_out = 0;
+    if (n_tensors == 0) return F3DGS_OK;
+    if (!tensors) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: null table", who);
+    if (!consts) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: null table of constants", who);
+    if (reinterpret_cast<uintptr_t>(consts) & 7) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: the table of constants must be 8-byte aligned", who);
+    size_t blocks = 0;
+    for (int i = 0; i < n_tensors; i++) {
+        const f3dgs_adam_device_tensor& t = tensors[i];
+        if (t.scheduled) {
+            if (t.max_steps <= 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: max_steps = %lld", who, i, t.max_steps);
+            if (t.lr_delay_steps < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: lr_delay_steps = %lld", who, i, t.lr_delay_steps);
+            if (!(t.lr_init >= 0.0) || !(t.lr_final >= 0.0) || ((t.lr_init == 0.0) != (t.lr_final == 0.0)))
+                return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: rates %g -> %g: both positive or both zero", who, i, t.lr_init, t.lr_final);
+        }
+        if (t.n == 0) continue;
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null pointer", who, i);
+        if (!t.step) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null step word", who, i);
+        if (!t.scheduled && !t.lr) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null rate word", who, i);
+        blocks += ((t.n + 3) / 4 + 255) / 256;
+    }
+    if (blocks >= (1ull << 31)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "%s: too large for one launch", who);
+    *blocks_out = blocks;
+    return F3DGS_OK;
+}
+
+}  // namespace
+
 }  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+int f3dgs_adam_step(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, double lr, double beta1,
+                    double beta2, double eps, int step, void* stream) {
+    return f3dgs_adam_step_rows(n, 1, nullptr, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, stream);
+}
+
+int f3dgs_adam_step_rows(size_t n, size_t width, const uint8_t* row_mask, float* param, const float* grad, float* exp_avg,
+                         float* exp_avg_sq, double lr, double beta1, double beta2, double eps, int step, void* stream) {
+    if (n == 0) return F3DGS_OK;
+    if (!param || !grad || !exp_avg || !exp_avg_sq) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (step < 1) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "step counts from 1");
+    if (row_mask && (width == 0 || n % width != 0 || width > 0xFFFFFFFFull))
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "n = %zu is not a whole number of rows of %zu floats", n, width);
+    launch_adam_step(n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, row_mask, width, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+int f3dgs_adam_step_multi(int n_tensors, const f3dgs_adam_tensor* tensors, double beta1, double beta2, double eps,
+                          const uint8_t* row_mask, size_t rows, void* stream) {
+    if (n_tensors < 0 || n_tensors > F3DGS_ADAM_MAX_TENSORS) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "0 .. %d tensors per call", F3DGS_ADAM_MAX_TENSORS);
+    if (n_tensors == 0) return F3DGS_OK;
+    if (!tensors) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null table");
+    size_t blocks = 0;
+    for (int i = 0; i < n_tensors; i++) {
+        const f3dgs_adam_tensor& t = tensors[i];
+        if (t.n == 0) continue;
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: null pointer", i);
+        if (t.step < 1) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: step counts from 1", i);
+        blocks += ((t.n + 3) / 4 + 255) / 256;
+    }
+    if (blocks >= (1ull << 31)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "too large for one launch");
+    if (row_mask && rows == 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "row mask without a row count");
+    launch_adam_step_multi(n_tensors, tensors, beta1, beta2, eps, row_mask, rows, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+int f3dgs_adam_schedule(int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2, long long* iteration,
+                        int advance, f3dgs_adam_consts* consts, void* stream) {
+    size_t blocks = 0;
+    if (int rc = check_adam_device_table("f3dgs_adam_schedule", n_tensors, tensors, beta1, beta2, consts, &blocks)) return rc;
+    if (n_tensors == 0) return F3DGS_OK;
+    for (int i = 0; i < n_tensors; i++)
+        if (tensors[i].scheduled && !iteration)
+            return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_schedule: tensor %d is scheduled, but there is no iteration word", i);
+    if (reinterpret_cast<uintptr_t>(iteration) & 7) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_schedule: misaligned iteration word");
+    launch_adam_schedule(n_tensors, tensors, beta1, beta2, iteration, advance, consts, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+int f3dgs_adam_step_multi_device(int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2, double eps,
+                                 const uint8_t* row_mask, size_t rows, const f3dgs_adam_consts* consts, void* stream) {
+    size_t blocks = 0;
+    if (int rc = check_adam_device_table("f3dgs_adam_step_multi_device", n_tensors, tensors, beta1, beta2, consts, &blocks)) return rc;
+    if (row_mask && rows == 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_step_multi_device: row mask without a row count");
+    if (n_tensors == 0) return F3DGS_OK;
+    launch_adam_step_multi_device(n_tensors, tensors, beta1, beta2, eps, row_mask, rows, consts, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+int f3dgs_reset_opacity(size_t n, float* raw, float* exp_avg, float* exp_avg_sq, float cap, void* stream) {
+    if (!(cap > 0.f && cap < 1.f)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_reset_opacity: cap = %g outside (0, 1)", (double)cap);
+    if (n == 0) return F3DGS_OK;
+    if (!raw) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_reset_opacity: null pointer");
+    if (n >= (1ull << 39)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "f3dgs_reset_opacity: too large for one launch");
+    launch_reset_opacity(n, raw, exp_avg, exp_avg_sq, cap, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+}  // extern "C"

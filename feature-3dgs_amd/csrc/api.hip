@@ -1,6 +1,12 @@
-// api.hip — extern "C" entry points of libf3dgs_hip.so (declared in include/f3dgs.h).
+// api.hip — the rasterizer's extern "C" entry points of libf3dgs_hip.so (declared in include/f3dgs.h), and what the library
+// shares.
 //
-// Host orchestration of the stages.  Replaces CudaRasterizer::Rasterizer::{markVisible,forward,backward}
+// Here: the version, the options, the last error (report_errorf: the library's one formatter), the setters that arm the next
+// call and the tile band; f3dgs_mark_visible, f3dgs_forward, f3dgs_backward; f3dgs_debug_read and the profile functions; and
+// f3dgs_contributions and f3dgs_label_votes, which carve the rasterizer's state buffers and read its frame notes.  Every other
+// operator defines its f3dgs_* entry points at the bottom of its own unit, beside the kernels and the scratch layout they guard.
+//
+// Host orchestration of the rasterizer's stages.  Replaces CudaRasterizer::Rasterizer::{markVisible,forward,backward}
 // (reference: submodules/diff-gaussian-rasterization-feature/cuda_rasterizer/rasterizer_impl.cu:141-153,
 // 198-342, 347-461).  Everything is enqueued on the caller's stream; the only host synchronisation is
 // the 4-byte read-back of num_rendered (same place as rasterizer_impl.cu:283).
@@ -11,7 +17,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <limits>
 #include <mutex>
 #include <string>
@@ -86,25 +91,15 @@ hipError_t zero_fill(void* p, size_t bytes, bool capturing, hipStream_t s) {
     return hipGetLastError();
 }
 
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 // The entry points that walk a finished forward call's lists (f3dgs_contributions, f3dgs_label_votes; `who` names one in the
 // messages): the checks they share of the call's sizes and of its state buffers ...
 int check_walk_call(const char* who, int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
                     const char* image_buffer) {
-    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
+    if (P < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
     if (R < 0 || width <= 0 || height <= 0)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: bad sizes (R = %d, image %d x %d)", who, R, width, height);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: bad sizes (R = %d, image %d x %d)", who, R, width, height);
     if (P > 0 && (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null state buffer", who);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: null state buffer", who);
     return F3DGS_OK;
 }
 // ... and what the launchers read of that state.  P == 0: no forward state, every tile is empty.  The sorted list sits at
@@ -128,23 +123,17 @@ WalkArgs walk_args(int P, int width, int height, const char* geom_buffer, const 
 
 }  // namespace
 
-int f3dgs::report_error(int code, const char* msg) { return fail(code, "%s", msg); }
 int f3dgs::report_errorf(int code, const char* fmt, ...) {
-    char buf[256];
+    char buf[512];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
-    return report_error(code, buf);
+    g_err = buf;
+    return code;
 }
 
 namespace {
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return fail(F3DGS_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // ---- optional per-stage profiling (F3DGS_PROFILE=1) ----------------------------------------------------
 // HIP events are recorded on the caller's stream around every stage and resolved lazily when the
@@ -262,7 +251,7 @@ int check_debug(int debug, hipStream_t s, const char* stage) {
     if (!debug) return F3DGS_OK;
     hipError_t e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return fail(F3DGS_ERR_HIP, "stage '%s' failed: %s", stage, hipGetErrorString(e));
+    if (e != hipSuccess) return report_errorf(F3DGS_ERR_HIP, "stage '%s' failed: %s", stage, hipGetErrorString(e));
     return F3DGS_OK;
 }
 
@@ -311,14 +300,6 @@ const OptionDesc kOptions[] = {
     {"dev", "F3DGS_DEV_BITS", &Options::dev, 0},
 #endif
 };
-
-// The per-Gaussian kernels read rotations, SH rows and feature rows - and write their gradients - with 16-byte accesses
-// (include/f3dgs.h, "Alignment"): a base pointer off a 16-byte boundary is refused here instead of faulting in a kernel.
-bool misaligned16(std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
-    return (bits & 15) != 0;
-}
 
 int tile_bits(int tiles) {
     int b = 0;
@@ -442,23 +423,23 @@ const uint32_t* f3dgs_depth_sort_info(void) {
 }
 
 int f3dgs_set_option(const char* name, int value) {
-    if (!name) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null option name");
+    if (!name) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null option name");
     for (const OptionDesc& d : kOptions)
         if (strcmp(d.name, name) == 0) {
             options().*(d.field) = value;
             return F3DGS_OK;
         }
-    return fail(F3DGS_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
+    return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
 }
 
 int f3dgs_get_option(const char* name, int* value) {
-    if (!name || !value) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null argument");
+    if (!name || !value) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null argument");
     for (const OptionDesc& d : kOptions)
         if (strcmp(d.name, name) == 0) {
             *value = options().*(d.field);
             return F3DGS_OK;
         }
-    return fail(F3DGS_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
+    return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
 }
 
 const char* f3dgs_option_name(int index) {
@@ -477,13 +458,13 @@ void f3dgs_set_feature_grad_accumulate(int on) { g_feature_accumulate = on ? 1 :
 
 int f3dgs_set_feature_grad_lowres(const float* gx, int Hg, int Wg, const float* scale) {
     if (!gx) { g_lowres = LowresGrad(); return F3DGS_OK; }
-    if (Hg <= 0 || Wg <= 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "bad low-resolution size %d x %d", Hg, Wg);
+    if (Hg <= 0 || Wg <= 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "bad low-resolution size %d x %d", Hg, Wg);
     g_lowres.gx = gx; g_lowres.scale = scale; g_lowres.Hg = Hg; g_lowres.Wg = Wg;
     return F3DGS_OK;
 }
 
 int f3dgs_debug_band_order(int gx, int gy, int tile_row_begin, int tile_row_end, uint32_t* tiles_out) {
-    if (gx <= 0 || gy <= 0 || !tiles_out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "bad grid");
+    if (gx <= 0 || gy <= 0 || !tiles_out) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "bad grid");
     int b0r, b1r;
     clamp_band(tile_row_begin, tile_row_end, gy, &b0r, &b1r);
     uint32_t b0 = 0, tb = 0;
@@ -507,9 +488,9 @@ void f3dgs_set_grad_rows_ready_callback(f3dgs_rows_fn fn, void* ctx, int chunks)
 int f3dgs_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                        uint8_t* present, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "P < 0");
+    if (P < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "P < 0");
     if (P == 0) return F3DGS_OK;
-    if (!means3D || !viewmatrix || !present) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!means3D || !viewmatrix || !present) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
     (void)projmatrix;
     launch_mark_visible(P, means3D, viewmatrix, present, s);
     HIP_TRY(hipGetLastError());
@@ -527,9 +508,9 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
     hipStream_t s = static_cast<hipStream_t>(stream);
     (void)prefiltered;  // the reference only uses it to __trap() on an impossible cull (auxiliary.h:162-166)
     if (num_rendered) *num_rendered = 0;
-    if (P < 0 || C < 0 || width <= 0 || height <= 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "bad sizes");
-    if (!geometry_resize || !binning_resize || !image_resize) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null resize hook");
-    if (!out_color || !out_depth || (C > 0 && !out_feature_map)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null output");
+    if (P < 0 || C < 0 || width <= 0 || height <= 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "bad sizes");
+    if (!geometry_resize || !binning_resize || !image_resize) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null resize hook");
+    if (!out_color || !out_depth || (C > 0 && !out_feature_map)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null output");
     const size_t HW = (size_t)width * height;
     if (P == 0) {  // rasterize_points.cu:84: outputs stay zero
         const bool cap0 = stream_is_capturing(s);      // (inside a graph: a kernel node, see zero_fill)
@@ -539,16 +520,16 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
         return F3DGS_OK;
     }
     if (!means3D || !opacities || !viewmatrix || !projmatrix || !background)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "null input");
-    if (!colors_precomp && !shs) return fail(F3DGS_ERR_INVALID_ARGUMENT, "need shs or colors_precomp");
-    if (!colors_precomp && !cam_pos) return fail(F3DGS_ERR_INVALID_ARGUMENT, "SH colours need cam_pos");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null input");
+    if (!colors_precomp && !shs) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "need shs or colors_precomp");
+    if (!colors_precomp && !cam_pos) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "SH colours need cam_pos");
     if (!cov3D_precomp && (!scales || !rotations))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "need scales+rotations or cov3D_precomp");
-    if (C > 0 && !semantic_feature) return fail(F3DGS_ERR_INVALID_ARGUMENT, "semantic_feature is null but C > 0");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "need scales+rotations or cov3D_precomp");
+    if (C > 0 && !semantic_feature) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "semantic_feature is null but C > 0");
     if (shs && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "SH degree %d needs %d coefficients, M = %d", D, (D + 1) * (D + 1), M);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "SH degree %d needs %d coefficients, M = %d", D, (D + 1) * (D + 1), M);
     if (misaligned16({shs, rotations, semantic_feature}))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "shs, rotations and semantic_feature must be 16-byte aligned (f3dgs.h, Alignment)");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "shs, rotations and semantic_feature must be 16-byte aligned (f3dgs.h, Alignment)");
 
     int rc = F3DGS_OK;
     ViewParams vp;
@@ -563,11 +544,11 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
     size_t geom_bytes = 0, img_bytes = 0, bin_bytes = 0;
     GeomState::carve(nullptr, P, &geom_bytes);
     char* geom_ptr = geometry_resize(geometry_ctx, geom_bytes);
-    if (!geom_ptr) return fail(F3DGS_ERR_ALLOC, "geometry buffer allocation of %zu bytes failed", geom_bytes);
+    if (!geom_ptr) return report_errorf(F3DGS_ERR_ALLOC, "geometry buffer allocation of %zu bytes failed", geom_bytes);
     GeomState geom = GeomState::carve(geom_ptr, P, nullptr);
     ImageState::carve(nullptr, HW, tiles, &img_bytes);
     char* img_ptr = image_resize(image_ctx, img_bytes);
-    if (!img_ptr) return fail(F3DGS_ERR_ALLOC, "image buffer allocation of %zu bytes failed", img_bytes);
+    if (!img_ptr) return report_errorf(F3DGS_ERR_ALLOC, "image buffer allocation of %zu bytes failed", img_bytes);
     ImageState img = ImageState::carve(img_ptr, HW, tiles, nullptr);
     // the single-pass sorts handle tile ids of up to two 8-bit digits (65536 tiles = 4096 x 4096 pixels and beyond
     // 4K); larger grids take the three-kernel passes
@@ -584,12 +565,12 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
     const int sf_opt = options().sync_free;
     const bool sync_free = !onesweep && (sf_opt > 0 || (sf_opt < 0 && capturing));
     if (capturing && !sync_free)
-        return fail(F3DGS_ERR_UNSUPPORTED, "the stream is being captured into a graph: the forward call reads the instance count on the host "
-                    "unless option sync_free is 1 or -1 (and sort_onesweep = 0)");
-    if (capturing && debug) return fail(F3DGS_ERR_UNSUPPORTED, "debug = 1 synchronises after every stage: not inside a graph capture");
+        return report_errorf(F3DGS_ERR_UNSUPPORTED, "the stream is being captured into a graph: the forward call reads the instance count on the host "
+                             "unless option sync_free is 1 or -1 (and sort_onesweep = 0)");
+    if (capturing && debug) return report_errorf(F3DGS_ERR_UNSUPPORTED, "debug = 1 synchronises after every stage: not inside a graph capture");
     int dev_index = 0;
     HIP_TRY(hipGetDevice(&dev_index));
-    if (dev_index < 0 || dev_index >= 64) return fail(F3DGS_ERR_UNSUPPORTED, "device index %d", dev_index);
+    if (dev_index < 0 || dev_index >= 64) return report_errorf(F3DGS_ERR_UNSUPPORTED, "device index %d", dev_index);
     CountHint& hint = g_count_hint[dev_index];
 
     StageTimer tm(s, !capturing);
@@ -605,9 +586,9 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
     // trip hides behind ~0.1 ms of GPU work instead of idling the device.
     CountReadback* rbp = count_readback(s, !capturing);
     if (!rbp)
-        return capturing ? fail(F3DGS_ERR_UNSUPPORTED, "graph capture: run one forward call on this stream (same host thread) before capturing - "
-                                "the pinned count words are allocated on a stream's first call")
-                         : fail(F3DGS_ERR_ALLOC, "pinned read-back buffer / event creation failed");
+        return capturing ? report_errorf(F3DGS_ERR_UNSUPPORTED, "graph capture: run one forward call on this stream (same host thread) before capturing - "
+                                         "the pinned count words are allocated on a stream's first call")
+                         : report_errorf(F3DGS_ERR_ALLOC, "pinned read-back buffer / event creation failed");
     CountReadback& rb = *rbp;
     if (capturing) rb.in_graph = true;
     g_last_forward_words = rb.host;
@@ -654,7 +635,7 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
         note_frame(geom_ptr, (onesweep || rb.host[2] != 0u) ? 1.f : 0.f, vp.band0, vp.band1);
         hint.known = true; hint.own = N; hint.ref = n_ref;
         known = true;
-        if (N >= (1u << 30) || n_ref >= (1u << 31)) return fail(F3DGS_ERR_UNSUPPORTED, "more than 2^30 instances");
+        if (N >= (1u << 30) || n_ref >= (1u << 31)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "more than 2^30 instances");
         return F3DGS_OK;
     };
     if (sync_free && (options().instance_capacity > 0 || hint.known)) {
@@ -666,8 +647,8 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
             want = SMALL_SORT_MAX;
         cap = (uint32_t)std::min(want, (1ull << 30) - 1ull);
     } else if (capturing) {
-        return fail(F3DGS_ERR_UNSUPPORTED, "graph capture: no provision for the instance lists - run one forward call on this thread and device "
-                    "before capturing, or set option instance_capacity");
+        return report_errorf(F3DGS_ERR_UNSUPPORTED, "graph capture: no provision for the instance lists - run one forward call on this thread and device "
+                             "before capturing, or set option instance_capacity");
     } else {      // the blocking read of the reference (and a sync-free thread's first frame on a device)
         if ((rc = read_counts())) return rc;
         cap = N;
@@ -681,7 +662,7 @@ int f3dgs_forward(f3dgs_resize_fn geometry_resize, void* geometry_ctx, f3dgs_res
         const uint32_t n_carve = known ? N : cap;           // entries the binning buffer holds in this round
         BinState::carve(nullptr, n_carve, &bin_bytes, tiles);
         char* bin_ptr = binning_resize(binning_ctx, bin_bytes);
-        if (!bin_ptr) return fail(F3DGS_ERR_ALLOC, "binning buffer allocation of %zu bytes failed", bin_bytes);
+        if (!bin_ptr) return report_errorf(F3DGS_ERR_ALLOC, "binning buffer allocation of %zu bytes failed", bin_bytes);
         bin = BinState::carve(bin_ptr, n_carve, nullptr, tiles);
         rb.host[3] = n_carve;
         // result must land in (tile_sorted, point_list) == the "A" side
@@ -758,31 +739,31 @@ int f3dgs_backward(int P, int D, int M, int C, int R, const float* background, i
     // taken before the first return, so that a pointer the caller may free after a failed or empty call never stays armed
     const LowresGrad lowres = g_lowres;
     g_lowres = LowresGrad();
-    if (P < 0 || C < 0 || R < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "bad sizes");
+    if (P < 0 || C < 0 || R < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "bad sizes");
     if (P == 0) return F3DGS_OK;
     if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "null state buffer");
-    if (!radii) return fail(F3DGS_ERR_INVALID_ARGUMENT, "radii is required");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null state buffer");
+    if (!radii) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "radii is required");
     if (lowres.gx) {
-        if (C == 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "a low-resolution feature-map gradient was set but C = 0");
+        if (C == 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "a low-resolution feature-map gradient was set but C = 0");
         if (lowres.Hg > height || lowres.Wg > width)
-            return fail(F3DGS_ERR_UNSUPPORTED, "low-resolution feature-map gradient %d x %d is larger than the image %d x %d: "
-                        "apply the transposed resize outside (f3dgs_feature_l1 with d_feature_map)", lowres.Hg, lowres.Wg, height, width);
+            return report_errorf(F3DGS_ERR_UNSUPPORTED, "low-resolution feature-map gradient %d x %d is larger than the image %d x %d: "
+                                 "apply the transposed resize outside (f3dgs_feature_l1 with d_feature_map)", lowres.Hg, lowres.Wg, height, width);
         if (!options().feature_mfma)
-            return fail(F3DGS_ERR_UNSUPPORTED, "the low-resolution feature-map gradient is taken by the pixel-lane backward (option feature_mfma = 1)");
+            return report_errorf(F3DGS_ERR_UNSUPPORTED, "the low-resolution feature-map gradient is taken by the pixel-lane backward (option feature_mfma = 1)");
     }
-    if (!dL_dpix || !dL_depths || (C > 0 && !dL_dfeaturepix && !lowres.gx)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null upstream grad");
+    if (!dL_dpix || !dL_depths || (C > 0 && !dL_dfeaturepix && !lowres.gx)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null upstream grad");
     if (!dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || (C > 0 && !dL_dsemantic_feature))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "null output");
-    if (M > 0 && shs && !dL_dsh) return fail(F3DGS_ERR_INVALID_ARGUMENT, "dL_dsh is null");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null output");
+    if (M > 0 && shs && !dL_dsh) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "dL_dsh is null");
     // as the forward call: the SH gradient of degree D fills (D + 1)^2 coefficients of an M-coefficient row
     if (shs && dL_dsh && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "SH degree %d needs %d coefficients, M = %d", D, (D + 1) * (D + 1), M);
-    if (scales && (!dL_dscale || !dL_drot || !rotations)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "scale/rot grads null");
-    if (!scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "scratch is null");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "SH degree %d needs %d coefficients, M = %d", D, (D + 1) * (D + 1), M);
+    if (scales && (!dL_dscale || !dL_drot || !rotations)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "scale/rot grads null");
+    if (!scratch) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "scratch is null");
     if (misaligned16({shs, rotations, dL_dsh, dL_drot, dL_dconic, dL_dsemantic_feature, scratch}))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "shs, rotations, dL_dsh, dL_drot, dL_dconic, dL_dsemantic_feature and scratch must be "
-                    "16-byte aligned (f3dgs.h, Alignment)");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "shs, rotations, dL_dsh, dL_drot, dL_dconic, dL_dsemantic_feature and scratch must be "
+                             "16-byte aligned (f3dgs.h, Alignment)");
 
     int rc = F3DGS_OK;
     ViewParams vp;
@@ -796,7 +777,7 @@ int f3dgs_backward(int P, int D, int M, int C, int R, const float* background, i
     float* grec = static_cast<float*>(scratch);
 
     const bool capturing = stream_is_capturing(s);      // (a step replayed from a graph: no events, no debug synchronisation)
-    if (capturing && debug) return fail(F3DGS_ERR_UNSUPPORTED, "debug = 1 synchronises after every stage: not inside a graph capture");
+    if (capturing && debug) return report_errorf(F3DGS_ERR_UNSUPPORTED, "debug = 1 synchronises after every stage: not inside a graph capture");
     StageTimer tm(s, !capturing);
     HIP_TRY(zero_fill(grec, (size_t)P * GREC * sizeof(float), capturing, s));
     // (f3dgs_set_feature_grad_accumulate: the caller's buffer already holds the sum over its earlier views)
@@ -861,11 +842,11 @@ int f3dgs_contributions(int P, int R, int width, int height, const char* geom_bu
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = check_walk_call("f3dgs_contributions", P, R, width, height, geom_buffer, binning_buffer, image_buffer)) return rc;
     if (K < 0 || K > F3DGS_CONTRIB_MAX_MASKS)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d masks, 0 .. %d are taken per call", K, F3DGS_CONTRIB_MAX_MASKS);
-    if (K > 0 && !masks) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d but masks is null", K);
-    if (K > 0 && !acc) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d masks but acc is null", K);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d masks, 0 .. %d are taken per call", K, F3DGS_CONTRIB_MAX_MASKS);
+    if (K > 0 && !masks) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d but masks is null", K);
+    if (K > 0 && !acc) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: K = %d masks but acc is null", K);
     if (!acc && !wmax && !alpha && !median_depth && !ids && !id_weight)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: every output is null");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_contributions: every output is null");
     if (P == 0) {      // no forward state: nothing blended anywhere; the per-Gaussian outputs have no rows
         if (!alpha && !median_depth && !ids && !id_weight) return F3DGS_OK;
         K = 0; masks = nullptr; acc = wmax = nullptr;
@@ -880,415 +861,16 @@ int f3dgs_label_votes(int P, int R, int width, int height, const char* geom_buff
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = check_walk_call("f3dgs_label_votes", P, R, width, height, geom_buffer, binning_buffer, image_buffer)) return rc;
     if (L < 1 || L > F3DGS_LABEL_VOTES_MAX_LABELS)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: L = %d labels, 1 .. %d are taken", L, F3DGS_LABEL_VOTES_MAX_LABELS);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: L = %d labels, 1 .. %d are taken", L, F3DGS_LABEL_VOTES_MAX_LABELS);
     if (labels_format != F3DGS_LABELS_U8 && labels_format != F3DGS_LABELS_I32 && labels_format != F3DGS_LABELS_I64)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: unknown labels format %d", labels_format);
-    if (!labels) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: labels is null");
-    if (!acc) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: acc is null");
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: unknown labels format %d", labels_format);
+    if (!labels) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: labels is null");
+    if (!acc) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: acc is null");
     const uintptr_t elem = labels_format == F3DGS_LABELS_U8 ? 1 : labels_format == F3DGS_LABELS_I32 ? 4 : 8;
     if (reinterpret_cast<uintptr_t>(labels) % elem)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: labels is off the alignment of its %d-byte element", (int)elem);
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_label_votes: labels is off the alignment of its %d-byte element", (int)elem);
     if (P == 0 || R == 0) return F3DGS_OK;      // nothing blended anywhere: nothing to add
     HIP_TRY(launch_label_votes(walk_args(P, width, height, geom_buffer, binning_buffer, image_buffer), labels, labels_format, L, acc, s));
-    return F3DGS_OK;
-}
-
-// nullptr if the sizes are taken, else the reason
-static const char* instance_bad_sizes(int P, int M, int L) {
-    if (P < 0) return "%s: P < 0 (P = %d, M = %d, L = %d)";
-    if (M < 1 || M > F3DGS_INSTANCE_MAX_MASKS) return "%s: bad sizes: M outside 1 .. 1024 (P = %d, M = %d, L = %d)";
-    if (L < 1 || L > F3DGS_INSTANCE_MAX_INSTANCES) return "%s: bad sizes: L outside 1 .. 4096 (P = %d, M = %d, L = %d)";
-    return nullptr;
-}
-
-size_t f3dgs_instance_scratch_bytes(int M, int L) {
-    if (instance_bad_sizes(0, M, L)) return 0;
-    return instance_scratch_bytes(M, L);
-}
-
-int f3dgs_instance_associate(int P, int M, int L, const float* acc_view, const float* acc, double iou_thresh, double min_weight,
-                             int32_t* count, int32_t* dropped, int32_t* mapping, int32_t* best_label, double* best_iou, float* table,
-                             void* scratch, void* stream) {
-    const char* who = "f3dgs_instance_associate";
-    if (const char* why = instance_bad_sizes(P, M, L)) return fail(F3DGS_ERR_INVALID_ARGUMENT, why, who, P, M, L);
-    if (!(iou_thresh >= 0.0)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: iou_thresh is negative or NaN", who);
-    if (!(min_weight >= 0.0)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: min_weight is negative or NaN", who);
-    if (!count || !dropped || !mapping || !best_label || !best_iou || !table || !scratch || (P > 0 && (!acc_view || !acc)))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
-    if (!aligned16(scratch)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
-    HIP_TRY(launch_instance_associate(P, M, L, acc_view, acc, iou_thresh, min_weight, count, dropped, mapping, best_label, best_iou, table,
-                                      static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_instance_merge(int P, int M, int L, float* acc_view, int clear_view, const int32_t* mapping, float* acc, void* stream) {
-    const char* who = "f3dgs_instance_merge";
-    if (const char* why = instance_bad_sizes(P, M, L)) return fail(F3DGS_ERR_INVALID_ARGUMENT, why, who, P, M, L);
-    if (!mapping || (P > 0 && (!acc_view || !acc))) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
-    if (P == 0) return F3DGS_OK;      // no rows: nothing to add
-    HIP_TRY(launch_instance_merge(P, M, L, acc_view, clear_view != 0, mapping, acc, static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-size_t f3dgs_feature_l1_scratch_bytes(int C, int Cout, int Hg, int Wg, int has_decoder) {
-    if (C <= 0 || Cout <= 0 || Hg <= 0 || Wg <= 0) return 0;
-    return feature_l1_scratch_bytes(C, Cout, Hg, Wg, has_decoder != 0);
-}
-
-int f3dgs_feature_l1(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
-                     const float* bias, const float* gt, float* loss, float* d_feature_map, float* d_weight,
-                     float* d_bias, void* scratch, void* stream) {
-    if (C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Hg <= 0 || Wg <= 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "bad sizes");
-    if (!feature_map || !gt || !loss || !scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
-    if ((weight == nullptr) != (bias == nullptr)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "weight and bias go together");
-    if (weight) {
-        if (!d_weight || !d_bias) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null decoder gradient");
-        if (!feature_l1_decoder_supported(C))
-            return fail(F3DGS_ERR_UNSUPPORTED, "decoder input width %d: supported are 32, 64, 128", C);
-    } else if (Cout != C) {
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "without a decoder the ground truth must have C = %d channels, got %d", C, Cout);
-    }
-    if ((long long)Hg * Wg * (long long)(Cout > C ? Cout : C) >= (1ll << 40)) return fail(F3DGS_ERR_UNSUPPORTED, "too large");
-    // the decoder kernels read W rows, the resized map and the sign bytes - arrays carved from `scratch` at multiples of 16
-    // bytes - and write g_x with 16-byte accesses
-    if (weight && misaligned16({weight, scratch}))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "with a decoder, weight and scratch must be 16-byte aligned (f3dgs.h, Alignment)");
-    HIP_TRY(launch_feature_l1(C, H, W, Cout, Hg, Wg, feature_map, weight, bias, gt, loss, d_feature_map, d_weight, d_bias,
-                              static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-const float* f3dgs_feature_l1_lowres_grad(int C, int Cout, int Hg, int Wg, int has_decoder, void* scratch) {
-    if (C <= 0 || Cout <= 0 || Hg <= 0 || Wg <= 0 || !scratch) return nullptr;
-    return feature_l1_lowres_grad(static_cast<char*>(scratch), C, Cout, Hg, Wg, has_decoder != 0);
-}
-
-size_t f3dgs_feature_decode_scratch_bytes(int C, int Hg, int Wg, int has_decoder) {
-    if (C <= 0 || Hg <= 0 || Wg <= 0) return 0;
-    return feature_decode_scratch_bytes(C, Hg, Wg, has_decoder != 0);
-}
-
-int f3dgs_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
-                         const float* bias, void* out, int out_is_half, void* scratch, void* stream) {
-    if (C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Hg <= 0 || Wg <= 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "bad sizes");
-    if (!feature_map || !out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
-    if ((weight == nullptr) != (bias == nullptr)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "weight and bias go together");
-    if (weight) {
-        if (!scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "scratch is null");
-        if (!feature_l1_decoder_supported(C))
-            return fail(F3DGS_ERR_UNSUPPORTED, "decoder input width %d: supported are 32, 64, 128", C);
-        if (misaligned16({weight, scratch}))       // 16-byte reads of W rows and of the resized map in `scratch`
-            return fail(F3DGS_ERR_INVALID_ARGUMENT, "with a decoder, weight and scratch must be 16-byte aligned (f3dgs.h, Alignment)");
-    } else if (Cout != C) {
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "without a decoder the output has C = %d channels, got %d", C, Cout);
-    }
-    HIP_TRY(launch_feature_decode(C, H, W, Cout, Hg, Wg, feature_map, weight, bias, out, out_is_half != 0,
-                                  static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-size_t f3dgs_segment_scratch_bytes(int C, int Cout, int Hs, int Ws, int K, int has_decoder) {
-    if (C <= 0 || Cout <= 0 || Hs < 0 || Ws < 0 || K <= 0 || (long long)Hs * Ws > (1ll << 30)) return 0;
-    return segment_scratch_bytes(C, Cout, Hs, Ws, K, has_decoder != 0);
-}
-
-int f3dgs_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const float* feature_map, const float* weight,
-                  const float* bias, const float* text, int flags, int64_t* labels, float* score, void* scratch, void* stream) {
-    if (C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Hs < 0 || Ws < 0 || K <= 0)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: bad sizes C=%d H=%d W=%d Cout=%d Hs=%d Ws=%d K=%d", C, H, W, Cout, Hs, Ws, K);
-    const int known = F3DGS_SEGMENT_ROUND_HALF | F3DGS_SEGMENT_TEXT_NORMALIZED;
-    if (flags & ~known) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: unknown flag bits 0x%x", flags & ~known);
-    if ((weight == nullptr) != (bias == nullptr)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: weight and bias go together");
-    if (!weight && Cout != C)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: without a decoder the text has C = %d channels, got %d", C, Cout);
-    if (K > F3DGS_SEGMENT_MAX_TEXTS) return fail(F3DGS_ERR_UNSUPPORTED, "segment: K=%d beyond the limit of %d text rows", K, F3DGS_SEGMENT_MAX_TEXTS);
-    if (weight && (!feature_l1_decoder_supported(C) || Cout % 32 != 0))
-        return fail(F3DGS_ERR_UNSUPPORTED, "segment: decoder %d -> %d: supported are input widths 32, 64, 128 and outputs that are multiples of 32", C, Cout);
-    if ((long long)Hs * Ws > (1ll << 30) || (long long)H * W > (1ll << 28)) return fail(F3DGS_ERR_UNSUPPORTED, "segment: too large");
-    if (Hs == 0 || Ws == 0) return F3DGS_OK;
-    const bool text_normalized = (flags & F3DGS_SEGMENT_TEXT_NORMALIZED) != 0;
-    if (!feature_map || !text || !labels) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: null pointer");
-    if (!scratch && (weight || !text_normalized)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "segment: scratch is null");
-    HIP_TRY(launch_segment(C, H, W, Cout, Hs, Ws, K, feature_map, weight, bias, text, (flags & F3DGS_SEGMENT_ROUND_HALF) != 0,
-                           text_normalized, labels, score, static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-// nullptr if the shape is served, else the reason
-static const char* feature_pca_unsupported(int C, long long HW, int stride, bool moments) {
-    if (C < 3) return "feature_pca: C = %d, at least 3 channels are needed for 3 components";
-    if (C > F3DGS_FEATURE_PCA_MAX_CHANNELS) return "feature_pca: C = %d beyond the limit of 4096 channels";
-    if (HW < 0 || HW > (1ll << 30)) return "feature_pca: C = %d: the map is too large";
-    if (moments && stride < 1) return "feature_pca: C = %d: stride < 1";
-    return nullptr;
-}
-
-size_t f3dgs_feature_pca_scratch_bytes(int C, long long HW, int stride) {
-    if (feature_pca_unsupported(C, HW, stride, true) || HW == 0) return 0;
-    return feature_pca_scratch_bytes(C, (size_t)HW, stride);
-}
-
-int f3dgs_feature_pca_moments(int C, long long HW, int stride, const float* feature_map, double* mean, double* cov, void* scratch,
-                              void* stream) {
-    if (const char* why = feature_pca_unsupported(C, HW, stride, true)) return fail(F3DGS_ERR_UNSUPPORTED, why, C);
-    if (HW == 0) return F3DGS_OK;
-    const long long n = (HW + stride - 1) / stride;
-    if (n < 3) return fail(F3DGS_ERR_UNSUPPORTED, "feature_pca: %lld samples (HW = %lld, stride = %d), at least 3 are needed", n, HW, stride);
-    if (!feature_map || !mean || !cov || !scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_moments: null pointer");
-    HIP_TRY(launch_feature_pca_moments(C, (size_t)HW, stride, feature_map, mean, cov, static_cast<char*>(scratch),
-                                       static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_feature_pca_project(int C, long long HW, const float* feature_map, const float* mean, const float* components,
-                              const float* lo, const float* hi, float* out, void* stream) {
-    if (const char* why = feature_pca_unsupported(C, HW, 1, false)) return fail(F3DGS_ERR_UNSUPPORTED, why, C);
-    if ((lo == nullptr) != (hi == nullptr)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_project: lo and hi go together");
-    if (HW == 0) return F3DGS_OK;
-    if (!feature_map || !mean || !components || !out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_project: null pointer");
-    HIP_TRY(launch_feature_pca_project(C, (size_t)HW, feature_map, mean, components, lo, hi, out, static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-// nullptr if the frame is served, else the reason
-static const char* view_unsupported(int H, int W, bool unprojects) {
-    if ((long long)H * W > (1ll << 30)) return "view: %d x %d pixels: the frame is too large";
-    if (unprojects && H > 0 && W > 0 && (H == 1 || W == 1))
-        return "view: %d x %d pixels: normals need at least 2 rows and 2 columns (x / (W - 1), y / (H - 1))";
-    return nullptr;
-}
-
-int f3dgs_view_normals(int H, int W, const float* depth, const float* proj, const double* inv_full_proj, float* out, int flags,
-                       void* stream) {
-    if (H < 0 || W < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_normals: bad sizes H=%d W=%d", H, W);
-    const int known = F3DGS_VIEW_NORMALS_CHW | F3DGS_VIEW_NORMALS_HALF;
-    if (flags & ~known) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_normals: unknown flag bits 0x%x", flags & ~known);
-    if (const char* why = view_unsupported(H, W, true)) return fail(F3DGS_ERR_UNSUPPORTED, why, H, W);
-    if (H == 0 || W == 0) return F3DGS_OK;
-    if (!depth || !proj || !inv_full_proj || !out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_normals: null pointer");
-    HIP_TRY(launch_view_normals(H, W, depth, proj, inv_full_proj, out, (flags & F3DGS_VIEW_NORMALS_CHW) != 0,
-                                (flags & F3DGS_VIEW_NORMALS_HALF) != 0, static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_view_gradient(int Cn, int H, int W, const float* image, float* out, float* minmax, void* stream) {
-    if (Cn < 1 || H < 0 || W < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_gradient: bad sizes Cn=%d H=%d W=%d", Cn, H, W);
-    if (const char* why = view_unsupported(H, W, false)) return fail(F3DGS_ERR_UNSUPPORTED, why, H, W);
-    if (H == 0 || W == 0) return F3DGS_OK;
-    if (!image || !out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_gradient: null pointer");
-    HIP_TRY(launch_view_gradient(Cn, H, W, image, out, minmax, static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_view_curvature(int H, int W, const float* depth, const float* proj, const double* inv_full_proj, float* out, float* minmax,
-                         void* stream) {
-    if (H < 0 || W < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_curvature: bad sizes H=%d W=%d", H, W);
-    if (const char* why = view_unsupported(H, W, true)) return fail(F3DGS_ERR_UNSUPPORTED, why, H, W);
-    if (H == 0 || W == 0) return F3DGS_OK;
-    if (!depth || !proj || !inv_full_proj || !out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_curvature: null pointer");
-    HIP_TRY(launch_view_curvature(H, W, depth, proj, inv_full_proj, out, minmax, static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_view_minmax(long long n, const float* field, float* minmax, void* stream) {
-    if (n < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_minmax: n = %lld", n);
-    if (n > (1ll << 30)) return fail(F3DGS_ERR_UNSUPPORTED, "view_minmax: %lld values: the field is too large", n);
-    if (n == 0) return F3DGS_OK;
-    if (!field || !minmax) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_minmax: null pointer");
-    HIP_TRY(launch_view_minmax((size_t)n, field, minmax, static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_view_palette(long long HW, const float* field, const float* minmax, const float* lut, int L, int mode, float* out_float,
-                       uint8_t* out_u8, void* stream) {
-    if (HW < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_palette: HW = %lld", HW);
-    if (mode != F3DGS_VIEW_PALETTE_MINMAX && mode != F3DGS_VIEW_PALETTE_MAX)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_palette: unknown mode %d", mode);
-    if (HW > (1ll << 30)) return fail(F3DGS_ERR_UNSUPPORTED, "view_palette: %lld pixels: the frame is too large", HW);
-    if (L < 2 || L > F3DGS_VIEW_PALETTE_MAX_ENTRIES)
-        return fail(F3DGS_ERR_UNSUPPORTED, "view_palette: a palette of %d entries: supported are 2 to %d", L, F3DGS_VIEW_PALETTE_MAX_ENTRIES);
-    if (HW == 0) return F3DGS_OK;
-    if (!field || !minmax || !lut || (!out_float && !out_u8)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_palette: null pointer");
-    HIP_TRY(launch_view_palette((size_t)HW, field, minmax, lut, L, mode, out_float, out_u8, static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_view_bytes(long long HW, const float* image, uint8_t* out_u8, void* stream) {
-    if (HW < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_bytes: HW = %lld", HW);
-    if (HW > (1ll << 30)) return fail(F3DGS_ERR_UNSUPPORTED, "view_bytes: %lld pixels: the frame is too large", HW);
-    if (HW == 0) return F3DGS_OK;
-    if (!image || !out_u8) return fail(F3DGS_ERR_INVALID_ARGUMENT, "view_bytes: null pointer");
-    HIP_TRY(launch_view_bytes((size_t)HW, image, out_u8, static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_adam_step(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, double lr, double beta1,
-                    double beta2, double eps, int step, void* stream) {
-    return f3dgs_adam_step_rows(n, 1, nullptr, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, stream);
-}
-
-int f3dgs_adam_step_rows(size_t n, size_t width, const uint8_t* row_mask, float* param, const float* grad, float* exp_avg,
-                         float* exp_avg_sq, double lr, double beta1, double beta2, double eps, int step, void* stream) {
-    if (n == 0) return F3DGS_OK;
-    if (!param || !grad || !exp_avg || !exp_avg_sq) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
-    if (step < 1) return fail(F3DGS_ERR_INVALID_ARGUMENT, "step counts from 1");
-    if (row_mask && (width == 0 || n % width != 0 || width > 0xFFFFFFFFull))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "n = %zu is not a whole number of rows of %zu floats", n, width);
-    launch_adam_step(n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, row_mask, width, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return F3DGS_OK;
-}
-
-int f3dgs_adam_step_multi(int n_tensors, const f3dgs_adam_tensor* tensors, double beta1, double beta2, double eps,
-                          const uint8_t* row_mask, size_t rows, void* stream) {
-    if (n_tensors < 0 || n_tensors > F3DGS_ADAM_MAX_TENSORS) return fail(F3DGS_ERR_INVALID_ARGUMENT, "0 .. %d tensors per call", F3DGS_ADAM_MAX_TENSORS);
-    if (n_tensors == 0) return F3DGS_OK;
-    if (!tensors) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null table");
-    size_t blocks = 0;
-    for (int i = 0; i < n_tensors; i++) {
-        const f3dgs_adam_tensor& t = tensors[i];
-        if (t.n == 0) continue;
-        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return fail(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: null pointer", i);
-        if (t.step < 1) return fail(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: step counts from 1", i);
-        blocks += ((t.n + 3) / 4 + 255) / 256;
-    }
-    if (blocks >= (1ull << 31)) return fail(F3DGS_ERR_UNSUPPORTED, "too large for one launch");
-    if (row_mask && rows == 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "row mask without a row count");
-    launch_adam_step_multi(n_tensors, tensors, beta1, beta2, eps, row_mask, rows, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return F3DGS_OK;
-}
-
-// The checks f3dgs_adam_schedule and f3dgs_adam_step_multi_device share: both take the same table.
-static int check_adam_device_table(const char* who, int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2,
-                                   const void* consts, size_t* blocks_out) {
-    if (n_tensors < 0 || n_tensors > F3DGS_ADAM_MAX_TENSORS)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: 0 .. %d tensors per call", who, F3DGS_ADAM_MAX_TENSORS);
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
-    *blocks_out = 0;
-    if (n_tensors == 0) return F3DGS_OK;
-    if (!tensors) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null table", who);
-    if (!consts) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null table of constants", who);
-    if (reinterpret_cast<uintptr_t>(consts) & 7) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: the table of constants must be 8-byte aligned", who);
-    size_t blocks = 0;
-    for (int i = 0; i < n_tensors; i++) {
-        const f3dgs_adam_device_tensor& t = tensors[i];
-        if (t.scheduled) {
-            if (t.max_steps <= 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: max_steps = %lld", who, i, t.max_steps);
-            if (t.lr_delay_steps < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: lr_delay_steps = %lld", who, i, t.lr_delay_steps);
-            if (!(t.lr_init >= 0.0) || !(t.lr_final >= 0.0) || ((t.lr_init == 0.0) != (t.lr_final == 0.0)))
-                return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: rates %g -> %g: both positive or both zero", who, i, t.lr_init, t.lr_final);
-        }
-        if (t.n == 0) continue;
-        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null pointer", who, i);
-        if (!t.step) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null step word", who, i);
-        if (!t.scheduled && !t.lr) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: tensor %d: null rate word", who, i);
-        blocks += ((t.n + 3) / 4 + 255) / 256;
-    }
-    if (blocks >= (1ull << 31)) return fail(F3DGS_ERR_UNSUPPORTED, "%s: too large for one launch", who);
-    *blocks_out = blocks;
-    return F3DGS_OK;
-}
-
-int f3dgs_adam_schedule(int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2, long long* iteration,
-                        int advance, f3dgs_adam_consts* consts, void* stream) {
-    size_t blocks = 0;
-    if (int rc = check_adam_device_table("f3dgs_adam_schedule", n_tensors, tensors, beta1, beta2, consts, &blocks)) return rc;
-    if (n_tensors == 0) return F3DGS_OK;
-    for (int i = 0; i < n_tensors; i++)
-        if (tensors[i].scheduled && !iteration)
-            return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_schedule: tensor %d is scheduled, but there is no iteration word", i);
-    if (reinterpret_cast<uintptr_t>(iteration) & 7) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_schedule: misaligned iteration word");
-    launch_adam_schedule(n_tensors, tensors, beta1, beta2, iteration, advance, consts, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return F3DGS_OK;
-}
-
-int f3dgs_adam_step_multi_device(int n_tensors, const f3dgs_adam_device_tensor* tensors, double beta1, double beta2, double eps,
-                                 const uint8_t* row_mask, size_t rows, const f3dgs_adam_consts* consts, void* stream) {
-    size_t blocks = 0;
-    if (int rc = check_adam_device_table("f3dgs_adam_step_multi_device", n_tensors, tensors, beta1, beta2, consts, &blocks)) return rc;
-    if (row_mask && rows == 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_adam_step_multi_device: row mask without a row count");
-    if (n_tensors == 0) return F3DGS_OK;
-    launch_adam_step_multi_device(n_tensors, tensors, beta1, beta2, eps, row_mask, rows, consts, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return F3DGS_OK;
-}
-
-int f3dgs_reset_opacity(size_t n, float* raw, float* exp_avg, float* exp_avg_sq, float cap, void* stream) {
-    if (!(cap > 0.f && cap < 1.f)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_reset_opacity: cap = %g outside (0, 1)", (double)cap);
-    if (n == 0) return F3DGS_OK;
-    if (!raw) return fail(F3DGS_ERR_INVALID_ARGUMENT, "f3dgs_reset_opacity: null pointer");
-    if (n >= (1ull << 39)) return fail(F3DGS_ERR_UNSUPPORTED, "f3dgs_reset_opacity: too large for one launch");
-    launch_reset_opacity(n, raw, exp_avg, exp_avg_sq, cap, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return F3DGS_OK;
-}
-
-int f3dgs_densify_gather(size_t n_out, const int32_t* src_row, const uint8_t* kind, const int32_t* override_row, int n_tensors,
-                         const f3dgs_densify_tensor* tensors, void* stream) {
-    if (n_tensors < 0 || n_tensors > F3DGS_DENSIFY_MAX_TENSORS)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "n_tensors = %d: at most %d per call", n_tensors, F3DGS_DENSIFY_MAX_TENSORS);
-    if (n_out == 0 || n_tensors == 0) return F3DGS_OK;
-    if (!src_row || !kind || !tensors) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
-    for (int i = 0; i < n_tensors; i++) {
-        const f3dgs_densify_tensor& t = tensors[i];
-        if (!t.src || !t.dst || t.width < 1) return fail(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: null pointer or width < 1", i);
-        if (t.width > 65536) return fail(F3DGS_ERR_UNSUPPORTED, "tensor %d: rows of %d floats (at most 65536)", i, t.width);
-        if (t.mode < F3DGS_DENSIFY_COPY || t.mode > F3DGS_DENSIFY_OVERRIDE_CHILD)
-            return fail(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: unknown mode %d", i, t.mode);
-        if (t.mode == F3DGS_DENSIFY_OVERRIDE_CHILD && (!t.override_src || !override_row))
-            return fail(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: OVERRIDE_CHILD needs override_src and override_row", i);
-    }
-    launch_densify_gather(n_out, src_row, kind, override_row, n_tensors, tensors, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return F3DGS_OK;
-}
-
-size_t f3dgs_knn_scratch_bytes(int P) { return knn_scratch_bytes((size_t)(P > 0 ? P : 0)); }
-
-int f3dgs_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* scratch, void* stream) {
-    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "P < 0");
-    if (P == 0) return F3DGS_OK;
-    if (!points || !mean_dist2 || !scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
-    launch_knn_mean_dist2(P, points, mean_dist2, static_cast<char*>(scratch), static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return F3DGS_OK;
-}
-
-size_t f3dgs_knn_neighbors_scratch_bytes(int P, int K) {
-    (void)K;      // the lists live in registers: the scratch is the front end's (sort buffers, sorted points, leaf boxes)
-    return knn_scratch_bytes((size_t)(P > 0 ? P : 0));
-}
-
-int f3dgs_knn_neighbors(int P, int K, const float* points, int32_t* idx, float* dist2, void* scratch, void* stream) {
-    const char* who = "f3dgs_knn_neighbors";
-    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
-    if (K < 1 || K > F3DGS_KNN_MAX_NEIGHBORS)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: K = %d neighbours, 1 .. %d are taken", who, K, F3DGS_KNN_MAX_NEIGHBORS);
-    if (P == 0) return F3DGS_OK;
-    if (P > (1 << 30)) return fail(F3DGS_ERR_UNSUPPORTED, "%s: more than 2^30 points", who);
-    if (!points || !idx || !scratch) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
-    if (!aligned16(scratch)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
-    HIP_TRY(launch_knn_neighbors(P, K, points, idx, dist2, static_cast<char*>(scratch), options().knn_outward != 0,
-                                 static_cast<hipStream_t>(stream)));
-    return F3DGS_OK;
-}
-
-int f3dgs_label_mode_filter(int P, int K, const int32_t* labels, const float* weight, const int32_t* idx, const float* dist2,
-                            float max_dist2, int fill, int32_t* labels_out, float* share_out, void* stream) {
-    const char* who = "f3dgs_label_mode_filter";
-    if (P < 0) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
-    if (K < 1 || K > F3DGS_KNN_MAX_NEIGHBORS)
-        return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: K = %d neighbours, 1 .. %d are taken", who, K, F3DGS_KNN_MAX_NEIGHBORS);
-    if (!(max_dist2 >= 0.f)) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: max_dist2 is negative or NaN", who);
-    if (P == 0) return F3DGS_OK;
-    if (!labels || !idx || !labels_out) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
-    if (labels_out == labels) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: labels_out is labels: a Jacobi step cannot run in place", who);
-    if (max_dist2 < INFINITY && !dist2) return fail(F3DGS_ERR_INVALID_ARGUMENT, "%s: a finite max_dist2 needs dist2", who);
-    HIP_TRY(launch_label_mode_filter(P, K, labels, weight, idx, dist2, max_dist2, fill != 0, labels_out, share_out,
-                                     static_cast<hipStream_t>(stream)));
     return F3DGS_OK;
 }
 
@@ -1328,7 +910,7 @@ int f3dgs_debug_read(const char* what, int P, int C, int R, int width, int heigh
     else if (w == "ranges") { src = img.ranges; bytes = tiles * 8; }
     else if (w == "final_T") { src = img.final_T; bytes = HW * 4; }
     else if (w == "n_contrib") { src = img.n_contrib; bytes = HW * 4; }
-    else return fail(F3DGS_ERR_INVALID_ARGUMENT, "unknown debug item '%s'", what);
+    else return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "unknown debug item '%s'", what);
     if (bytes > dst_bytes) bytes = dst_bytes;
     if (bytes) {
         HIP_TRY(hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, s));

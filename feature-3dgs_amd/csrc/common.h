@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <initializer_list>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -403,71 +404,32 @@ void launch_iota(uint32_t* dst, size_t n, hipStream_t s);
 void launch_radix_sort_keys_to_order(const uint32_t* keys, uint32_t* key_a, uint32_t* val_a, uint32_t* key_b, uint32_t* val_b,
                                      size_t n, int nbits, uint32_t* hist, hipStream_t s);
 
-// feature_loss.hip
-size_t feature_l1_scratch_bytes(int C, int Cout, int Hg, int Wg, bool decoder);
-bool feature_l1_decoder_supported(int C);
-const float* feature_l1_lowres_grad(char* scratch, int C, int Cout, int Hg, int Wg, bool decoder);   // (Hg Wg, C) pixel-major
-hipError_t launch_feature_l1(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
-                             const float* bias, const float* gt, float* loss, float* d_feature_map, float* d_weight,
-                             float* d_bias, char* scratch, hipStream_t s);
+// The entry points of an operator (its f3dgs_* functions, their argument checks and scratch carving) are defined in the
+// operator's own unit, beside its kernels; declared below is only what one unit calls of another.
+// api.hip: sets the text f3dgs_last_error() returns (at most 511 characters) and returns `code` - the one formatter of the library
+int report_errorf(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// (inside an entry point) a HIP call or a launcher that returns hipError_t: its failure is the call's
+#define HIP_TRY(expr)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) return report_errorf(F3DGS_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
 
-size_t feature_decode_scratch_bytes(int C, int Hg, int Wg, bool decoder);
-hipError_t launch_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
-                                 const float* bias, void* out, bool half, char* scratch, hipStream_t s);
-// the decode's resize stage alone: (C,H,W) -> pixel-major X[Hg Wg][C] (segment.hip feeds its own decoder loop from it)
+// The per-Gaussian kernels read rotations, SH rows and feature rows - and write their gradients - with 16-byte accesses
+// (include/f3dgs.h, "Alignment"): a base pointer off a 16-byte boundary is refused by the entry point instead of faulting in a kernel.
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool misaligned16(std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 15) != 0;
+}
+
+// feature_loss.hip, for segment.hip: the decoder widths served, and the decode's resize stage alone: (C,H,W) -> pixel-major
+// X[Hg Wg][C] (segment.hip feeds its own decoder loop from it)
+bool feature_l1_decoder_supported(int C);
 void launch_feature_resize(int C, int H, int W, int Hg, int Wg, const float* feature_map, float* X, hipStream_t s);
 
-// segment.hip
-size_t segment_scratch_bytes(int C, int Cout, int Hs, int Ws, int K, bool decoder);
-hipError_t launch_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const float* feature_map, const float* weight,
-                          const float* bias, const float* text, bool round_half, bool text_normalized, int64_t* labels,
-                          float* score, char* scratch, hipStream_t s);
-
-// feature_pca.hip
-size_t feature_pca_scratch_bytes(int C, size_t HW, int stride);
-hipError_t launch_feature_pca_moments(int C, size_t HW, int stride, const float* feature_map, double* mean, double* cov,
-                                      char* scratch, hipStream_t s);
-hipError_t launch_feature_pca_project(int C, size_t HW, const float* feature_map, const float* mean, const float* components,
-                                      const float* lo, const float* hi, float* out, hipStream_t s);
-
-// view_modes.hip
-hipError_t launch_view_normals(int H, int W, const float* depth, const float* proj, const double* inv, float* out, bool chw, bool half,
-                               hipStream_t s);
-hipError_t launch_view_gradient(int Cn, int H, int W, const float* image, float* out, float* minmax, hipStream_t s);
-hipError_t launch_view_curvature(int H, int W, const float* depth, const float* proj, const double* inv, float* out, float* minmax,
-                                 hipStream_t s);
-hipError_t launch_view_minmax(size_t n, const float* field, float* minmax, hipStream_t s);
-hipError_t launch_view_palette(size_t HW, const float* field, const float* minmax, const float* lut, int L, int mode, float* out_float,
-                               unsigned char* out_u8, hipStream_t s);
-hipError_t launch_view_bytes(size_t HW, const float* image, unsigned char* out, hipStream_t s);
-
-// api.hip: sets the text f3dgs_last_error() returns (for the entry points defined in other files); returns `code`
-int report_error(int code, const char* msg);
-int report_errorf(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// adam.hip
-void launch_adam_step(size_t n, float* p, const float* g, float* m, float* v, double lr, double b1, double b2, double eps,
-                      int step, const uint8_t* row_mask, size_t width, hipStream_t s);
-
-void launch_adam_step_multi(int count, const f3dgs_adam_tensor* tensors, double b1, double b2, double eps, const uint8_t* row_mask,
-                            size_t rows, hipStream_t s);
-
-void launch_adam_schedule(int count, const f3dgs_adam_device_tensor* tensors, double b1, double b2, long long* iteration, int advance,
-                          f3dgs_adam_consts* consts, hipStream_t s);
-void launch_adam_step_multi_device(int count, const f3dgs_adam_device_tensor* tensors, double b1, double b2, double eps,
-                                   const uint8_t* row_mask, size_t rows, const f3dgs_adam_consts* consts, hipStream_t s);
-void launch_reset_opacity(size_t n, float* raw, float* exp_avg, float* exp_avg_sq, float cap, hipStream_t s);
-
-// densify.hip
-using DensifyTensor = f3dgs_densify_tensor;
-constexpr int DENSIFY_MAX_TENSORS = F3DGS_DENSIFY_MAX_TENSORS;
-constexpr int DENSIFY_ZERO_NEW = F3DGS_DENSIFY_ZERO_NEW, DENSIFY_OVERRIDE_CHILD = F3DGS_DENSIFY_OVERRIDE_CHILD;
-void launch_densify_gather(size_t n_out, const int32_t* src_row, const uint8_t* kind, const int32_t* override_row, int n_tensors,
-                           const DensifyTensor* tensors, hipStream_t s);
-
-// knn.hip
+// knn.hip, for neighbors.hip
 constexpr int KNN_LEAF = 256;        // sorted points per leaf
 struct KnnBox {
     float lo[3], hi[3];
@@ -476,12 +438,6 @@ size_t knn_scratch_bytes(size_t P);
 // The front end of every search: bounds, 30-bit Morton codes, the radix sort, the gather.  *sorted (P x {x, y, z, original index
 // as bits}, Morton order) and *leaf_box (*n_leaf = ceil(P / KNN_LEAF) boxes) point into `scratch` (knn_scratch_bytes(P), P >= 1).
 void launch_knn_sort(int P, const float* points, char* scratch, float4** sorted, KnnBox** leaf_box, int* n_leaf, hipStream_t s);
-void launch_knn_mean_dist2(int P, const float* points, float* out, char* scratch, hipStream_t s);
-// neighbors.hip (built with -ffp-contract=off): the K nearest neighbours with indices (f3dgs_knn_neighbors; scratch as above;
-// `outward`: option knn_outward) and the mode filter over them (f3dgs_label_mode_filter)
-hipError_t launch_knn_neighbors(int P, int K, const float* points, int* idx, float* dist2, char* scratch, bool outward, hipStream_t s);
-hipError_t launch_label_mode_filter(int P, int K, const int* labels, const float* weight, const int* idx, const float* dist2,
-                                    float max_dist2, bool fill, int* labels_out, float* share_out, hipStream_t s);
 
 // render_fwd.hip / render_bwd.hip
 // `tile_len` (zero-filled by the caller): receives the longest walk of every tile (max n_contrib of its pixels)
@@ -522,12 +478,6 @@ hipError_t launch_contributions(const WalkArgs& walk, int K, const float* masks,
                                 float* median_depth, int* ids, float* id_weight, hipStream_t s);
 // contrib.hip: the label vote over the same lists (f3dgs_label_votes): acc (P x (L + 1)) over the one-hot masks of `labels`
 hipError_t launch_label_votes(const WalkArgs& walk, const void* labels, int format, int L, float* acc, hipStream_t s);
-// instances.hip: one view's masks against the 3D instances built so far (f3dgs_instance_associate, f3dgs_instance_merge)
-size_t instance_scratch_bytes(int M, int L);
-hipError_t launch_instance_associate(int P, int M, int L, const float* acc_view, const float* acc, double iou_thresh, double min_weight,
-                                     int* count, int* dropped, int* mapping, int* best_label, double* best_iou, float* table,
-                                     char* scratch, hipStream_t s);
-hipError_t launch_instance_merge(int P, int M, int L, float* acc_view, bool clear_view, const int* mapping, float* acc, hipStream_t s);
 struct BwdArgs;
 void launch_render_backward_pl(BwdArgs a, int C, hipStream_t s);     // render_bwd_pl.hip
 void launch_tile_order(const uint32_t* tile_len, size_t tiles, uint32_t* order, uint32_t band_b0, uint32_t band_tb, hipStream_t s);

@@ -21,6 +21,10 @@ namespace f3dgs {
 
 namespace {
 
+using DensifyTensor = f3dgs_densify_tensor;
+constexpr int DENSIFY_MAX_TENSORS = F3DGS_DENSIFY_MAX_TENSORS;
+constexpr int DENSIFY_ZERO_NEW = F3DGS_DENSIFY_ZERO_NEW, DENSIFY_OVERRIDE_CHILD = F3DGS_DENSIFY_OVERRIDE_CHILD;
+
 struct GatherTable {
     DensifyTensor t[DENSIFY_MAX_TENSORS];
 };
@@ -66,8 +70,6 @@ densify_gather_kernel(size_t n_out, const int32_t* __restrict__ src_row, const u
     }
 }
 
-}  // namespace
-
 void launch_densify_gather(size_t n_out, const int32_t* src_row, const uint8_t* kind, const int32_t* override_row, int n_tensors,
                            const DensifyTensor* tensors, hipStream_t s) {
     if (n_out == 0 || n_tensors == 0) return;
@@ -82,4 +84,32 @@ void launch_densify_gather(size_t n_out, const int32_t* src_row, const uint8_t* 
     hipLaunchKernelGGL(densify_gather_kernel, dim3((unsigned)blocks, n_tensors), dim3(256), 0, s, n_out, src_row, kind, override_row, tab);
 }
 
+}  // namespace
+
 }  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+int f3dgs_densify_gather(size_t n_out, const int32_t* src_row, const uint8_t* kind, const int32_t* override_row, int n_tensors,
+                         const f3dgs_densify_tensor* tensors, void* stream) {
+    if (n_tensors < 0 || n_tensors > F3DGS_DENSIFY_MAX_TENSORS)
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "n_tensors = %d: at most %d per call", n_tensors, F3DGS_DENSIFY_MAX_TENSORS);
+    if (n_out == 0 || n_tensors == 0) return F3DGS_OK;
+    if (!src_row || !kind || !tensors) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
+    for (int i = 0; i < n_tensors; i++) {
+        const f3dgs_densify_tensor& t = tensors[i];
+        if (!t.src || !t.dst || t.width < 1) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: null pointer or width < 1", i);
+        if (t.width > 65536) return report_errorf(F3DGS_ERR_UNSUPPORTED, "tensor %d: rows of %d floats (at most 65536)", i, t.width);
+        if (t.mode < F3DGS_DENSIFY_COPY || t.mode > F3DGS_DENSIFY_OVERRIDE_CHILD)
+            return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: unknown mode %d", i, t.mode);
+        if (t.mode == F3DGS_DENSIFY_OVERRIDE_CHILD && (!t.override_src || !override_row))
+            return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "tensor %d: OVERRIDE_CHILD needs override_src and override_row", i);
+    }
+    launch_densify_gather(n_out, src_row, kind, override_row, n_tensors, tensors, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
+}
+
+}  // extern "C"

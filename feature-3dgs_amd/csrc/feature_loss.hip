@@ -497,15 +497,11 @@ hipError_t run_decoder(int N, int Cout, const Scratch& sc, const float* Wd, cons
     return hipGetLastError();
 }
 
-}  // namespace
-
 size_t feature_l1_scratch_bytes(int C, int Cout, int Hg, int Wg, bool decoder) {
     size_t b = 0;
     Scratch::carve(nullptr, C, Cout, Hg * Wg, decoder, &b);
     return b;
 }
-
-bool feature_l1_decoder_supported(int C) { return C == 32 || C == 64 || C == 128; }
 
 const float* feature_l1_lowres_grad(char* scratch, int C, int Cout, int Hg, int Wg, bool decoder) {
     return Scratch::carve(scratch, C, Cout, Hg * Wg, decoder, nullptr).GX;
@@ -516,7 +512,7 @@ size_t feature_decode_scratch_bytes(int C, int Hg, int Wg, bool decoder) {
 }
 
 template <int C>
-static hipError_t run_decode(int N, int Cout, const float* X, const float* Wd, const float* bias, void* out, bool half, hipStream_t s) {
+hipError_t run_decode(int N, int Cout, const float* X, const float* Wd, const float* bias, void* out, bool half, hipStream_t s) {
     const size_t lds = sizeof(GemmLds<C>);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fl_decode_kernel<C, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -543,12 +539,6 @@ hipError_t launch_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, 
     if (C == 64) return run_decode<64>(N, Cout, X, weight, bias, out, half, s);
     if (C == 128) return run_decode<128>(N, Cout, X, weight, bias, out, half, s);
     return hipErrorInvalidValue;
-}
-
-void launch_feature_resize(int C, int H, int W, int Hg, int Wg, const float* feature_map, float* X, hipStream_t s) {
-    const int N = Hg * Wg;
-    hipLaunchKernelGGL(fl_resize_kernel, dim3((N + 63) / 64, (C + 31) / 32), dim3(256), 0, s, make_resize_geom(H, W, Hg, Wg), C,
-                       feature_map, X, nullptr, 0.f, nullptr);
 }
 
 hipError_t launch_feature_l1(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
@@ -578,4 +568,77 @@ hipError_t launch_feature_l1(int C, int H, int W, int Cout, int Hg, int Wg, cons
     return hipGetLastError();
 }
 
+}  // namespace
+
+bool feature_l1_decoder_supported(int C) { return C == 32 || C == 64 || C == 128; }
+
+void launch_feature_resize(int C, int H, int W, int Hg, int Wg, const float* feature_map, float* X, hipStream_t s) {
+    const int N = Hg * Wg;
+    hipLaunchKernelGGL(fl_resize_kernel, dim3((N + 63) / 64, (C + 31) / 32), dim3(256), 0, s, make_resize_geom(H, W, Hg, Wg), C,
+                       feature_map, X, nullptr, 0.f, nullptr);
+}
+
 }  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+size_t f3dgs_feature_l1_scratch_bytes(int C, int Cout, int Hg, int Wg, int has_decoder) {
+    if (C <= 0 || Cout <= 0 || Hg <= 0 || Wg <= 0) return 0;
+    return feature_l1_scratch_bytes(C, Cout, Hg, Wg, has_decoder != 0);
+}
+
+int f3dgs_feature_l1(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
+                     const float* bias, const float* gt, float* loss, float* d_feature_map, float* d_weight,
+                     float* d_bias, void* scratch, void* stream) {
+    if (C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Hg <= 0 || Wg <= 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "bad sizes");
+    if (!feature_map || !gt || !loss || !scratch) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
+    if ((weight == nullptr) != (bias == nullptr)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "weight and bias go together");
+    if (weight) {
+        if (!d_weight || !d_bias) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null decoder gradient");
+        if (!feature_l1_decoder_supported(C))
+            return report_errorf(F3DGS_ERR_UNSUPPORTED, "decoder input width %d: supported are 32, 64, 128", C);
+    } else if (Cout != C) {
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "without a decoder the ground truth must have C = %d channels, got %d", C, Cout);
+    }
+    if ((long long)Hg * Wg * (long long)(Cout > C ? Cout : C) >= (1ll << 40)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "too large");
+    // the decoder kernels read W rows, the resized map and the sign bytes - arrays carved from `scratch` at multiples of 16
+    // bytes - and write g_x with 16-byte accesses
+    if (weight && misaligned16({weight, scratch}))
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "with a decoder, weight and scratch must be 16-byte aligned (f3dgs.h, Alignment)");
+    HIP_TRY(launch_feature_l1(C, H, W, Cout, Hg, Wg, feature_map, weight, bias, gt, loss, d_feature_map, d_weight, d_bias,
+                              static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+const float* f3dgs_feature_l1_lowres_grad(int C, int Cout, int Hg, int Wg, int has_decoder, void* scratch) {
+    if (C <= 0 || Cout <= 0 || Hg <= 0 || Wg <= 0 || !scratch) return nullptr;
+    return feature_l1_lowres_grad(static_cast<char*>(scratch), C, Cout, Hg, Wg, has_decoder != 0);
+}
+
+size_t f3dgs_feature_decode_scratch_bytes(int C, int Hg, int Wg, int has_decoder) {
+    if (C <= 0 || Hg <= 0 || Wg <= 0) return 0;
+    return feature_decode_scratch_bytes(C, Hg, Wg, has_decoder != 0);
+}
+
+int f3dgs_feature_decode(int C, int H, int W, int Cout, int Hg, int Wg, const float* feature_map, const float* weight,
+                         const float* bias, void* out, int out_is_half, void* scratch, void* stream) {
+    if (C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Hg <= 0 || Wg <= 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "bad sizes");
+    if (!feature_map || !out) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
+    if ((weight == nullptr) != (bias == nullptr)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "weight and bias go together");
+    if (weight) {
+        if (!scratch) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "scratch is null");
+        if (!feature_l1_decoder_supported(C))
+            return report_errorf(F3DGS_ERR_UNSUPPORTED, "decoder input width %d: supported are 32, 64, 128", C);
+        if (misaligned16({weight, scratch}))       // 16-byte reads of W rows and of the resized map in `scratch`
+            return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "with a decoder, weight and scratch must be 16-byte aligned (f3dgs.h, Alignment)");
+    } else if (Cout != C) {
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "without a decoder the output has C = %d channels, got %d", C, Cout);
+    }
+    HIP_TRY(launch_feature_decode(C, H, W, Cout, Hg, Wg, feature_map, weight, bias, out, out_is_half != 0,
+                                  static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+}  // extern "C"

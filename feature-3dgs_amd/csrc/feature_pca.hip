@@ -284,8 +284,6 @@ __global__ void __launch_bounds__(256) pca_project_kernel(int C, size_t HW, cons
     for (int k = 0; k < 3; k++) out[p * 3 + k] = t[k];
 }
 
-}  // namespace
-
 size_t feature_pca_scratch_bytes(int C, size_t HW, int stride) {
     size_t b = 0;
     PcaScratch::carve(nullptr, C, pca_geom(C, HW, stride), &b);
@@ -316,4 +314,48 @@ hipError_t launch_feature_pca_project(int C, size_t HW, const float* feature_map
     return hipGetLastError();
 }
 
+// nullptr if the shape is served, else the reason
+const char* feature_pca_unsupported(int C, long long HW, int stride, bool moments) {
+    if (C < 3) return "feature_pca: C = %d, at least 3 channels are needed for 3 components";
+    if (C > F3DGS_FEATURE_PCA_MAX_CHANNELS) return "feature_pca: C = %d beyond the limit of 4096 channels";
+    if (HW < 0 || HW > (1ll << 30)) return "feature_pca: C = %d: the map is too large";
+    if (moments && stride < 1) return "feature_pca: C = %d: stride < 1";
+    return nullptr;
+}
+
+}  // namespace
+
 }  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+size_t f3dgs_feature_pca_scratch_bytes(int C, long long HW, int stride) {
+    if (feature_pca_unsupported(C, HW, stride, true) || HW == 0) return 0;
+    return feature_pca_scratch_bytes(C, (size_t)HW, stride);
+}
+
+int f3dgs_feature_pca_moments(int C, long long HW, int stride, const float* feature_map, double* mean, double* cov, void* scratch,
+                              void* stream) {
+    if (const char* why = feature_pca_unsupported(C, HW, stride, true)) return report_errorf(F3DGS_ERR_UNSUPPORTED, why, C);
+    if (HW == 0) return F3DGS_OK;
+    const long long n = (HW + stride - 1) / stride;
+    if (n < 3) return report_errorf(F3DGS_ERR_UNSUPPORTED, "feature_pca: %lld samples (HW = %lld, stride = %d), at least 3 are needed", n, HW, stride);
+    if (!feature_map || !mean || !cov || !scratch) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_moments: null pointer");
+    HIP_TRY(launch_feature_pca_moments(C, (size_t)HW, stride, feature_map, mean, cov, static_cast<char*>(scratch),
+                                       static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_feature_pca_project(int C, long long HW, const float* feature_map, const float* mean, const float* components,
+                              const float* lo, const float* hi, float* out, void* stream) {
+    if (const char* why = feature_pca_unsupported(C, HW, 1, false)) return report_errorf(F3DGS_ERR_UNSUPPORTED, why, C);
+    if ((lo == nullptr) != (hi == nullptr)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_project: lo and hi go together");
+    if (HW == 0) return F3DGS_OK;
+    if (!feature_map || !mean || !components || !out) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "feature_pca_project: null pointer");
+    HIP_TRY(launch_feature_pca_project(C, (size_t)HW, feature_map, mean, components, lo, hi, out, static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+}  // extern "C"

@@ -292,8 +292,6 @@ int inst_grid(int P) {
     return (int)std::min<long long>(std::max<long long>(blocks, 1), 256 * 8);      // 8 workgroups = 32 waves per CU
 }
 
-}  // namespace
-
 size_t instance_scratch_bytes(int M, int L) {
     size_t b = 0;
     InstScratch::carve(nullptr, M, L, &b);
@@ -325,4 +323,49 @@ hipError_t launch_instance_merge(int P, int M, int L, float* acc_view, bool clea
     return hipGetLastError();
 }
 
+// nullptr if the sizes are taken, else the reason
+const char* instance_bad_sizes(int P, int M, int L) {
+    if (P < 0) return "%s: P < 0 (P = %d, M = %d, L = %d)";
+    if (M < 1 || M > F3DGS_INSTANCE_MAX_MASKS) return "%s: bad sizes: M outside 1 .. 1024 (P = %d, M = %d, L = %d)";
+    if (L < 1 || L > F3DGS_INSTANCE_MAX_INSTANCES) return "%s: bad sizes: L outside 1 .. 4096 (P = %d, M = %d, L = %d)";
+    return nullptr;
+}
+
+}  // namespace
+
 }  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+size_t f3dgs_instance_scratch_bytes(int M, int L) {
+    if (instance_bad_sizes(0, M, L)) return 0;
+    return instance_scratch_bytes(M, L);
+}
+
+int f3dgs_instance_associate(int P, int M, int L, const float* acc_view, const float* acc, double iou_thresh, double min_weight,
+                             int32_t* count, int32_t* dropped, int32_t* mapping, int32_t* best_label, double* best_iou, float* table,
+                             void* scratch, void* stream) {
+    const char* who = "f3dgs_instance_associate";
+    if (const char* why = instance_bad_sizes(P, M, L)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, why, who, P, M, L);
+    if (!(iou_thresh >= 0.0)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: iou_thresh is negative or NaN", who);
+    if (!(min_weight >= 0.0)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: min_weight is negative or NaN", who);
+    if (!count || !dropped || !mapping || !best_label || !best_iou || !table || !scratch || (P > 0 && (!acc_view || !acc)))
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (!aligned16(scratch)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+    HIP_TRY(launch_instance_associate(P, M, L, acc_view, acc, iou_thresh, min_weight, count, dropped, mapping, best_label, best_iou, table,
+                                      static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_instance_merge(int P, int M, int L, float* acc_view, int clear_view, const int32_t* mapping, float* acc, void* stream) {
+    const char* who = "f3dgs_instance_merge";
+    if (const char* why = instance_bad_sizes(P, M, L)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, why, who, P, M, L);
+    if (!mapping || (P > 0 && (!acc_view || !acc))) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (P == 0) return F3DGS_OK;      // no rows: nothing to add
+    HIP_TRY(launch_instance_merge(P, M, L, acc_view, clear_view != 0, mapping, acc, static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+}  // extern "C"

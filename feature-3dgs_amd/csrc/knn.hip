@@ -183,6 +183,14 @@ __global__ void __launch_bounds__(64) knn_query_kernel(int P, const float4* __re
     if (have) out[__float_as_uint(q.w)] = (b0 + b1 + b2) / 3.0f;
 }
 
+void launch_knn_mean_dist2(int P, const float* points, float* out, char* scratch, hipStream_t s) {
+    float4* sorted;
+    Box* leaf_box;
+    int n_leaf;
+    launch_knn_sort(P, points, scratch, &sorted, &leaf_box, &n_leaf, s);
+    hipLaunchKernelGGL(knn_query_kernel, dim3((P + 63) / 64), dim3(64), 0, s, P, sorted, leaf_box, n_leaf, out);
+}
+
 }  // namespace
 
 size_t knn_scratch_bytes(size_t P) {
@@ -219,12 +227,21 @@ void launch_knn_sort(int P, const float* points, char* scratch, float4** sorted_
     *n_leaf_out = n_leaf;
 }
 
-void launch_knn_mean_dist2(int P, const float* points, float* out, char* scratch, hipStream_t s) {
-    float4* sorted;
-    Box* leaf_box;
-    int n_leaf;
-    launch_knn_sort(P, points, scratch, &sorted, &leaf_box, &n_leaf, s);
-    hipLaunchKernelGGL(knn_query_kernel, dim3((P + 63) / 64), dim3(64), 0, s, P, sorted, leaf_box, n_leaf, out);
+}  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+size_t f3dgs_knn_scratch_bytes(int P) { return knn_scratch_bytes((size_t)(P > 0 ? P : 0)); }
+
+int f3dgs_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* scratch, void* stream) {
+    if (P < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "P < 0");
+    if (P == 0) return F3DGS_OK;
+    if (!points || !mean_dist2 || !scratch) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "null pointer");
+    launch_knn_mean_dist2(P, points, mean_dist2, static_cast<char*>(scratch), static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return F3DGS_OK;
 }
 
-}  // namespace f3dgs
+}  // extern "C"

@@ -188,8 +188,6 @@ void launch_lists(int P, int K, const float4* sorted, const KnnBox* leaf_box, in
         hipLaunchKernelGGL((knn_list_kernel<16, OUTWARD>), grid, block, 0, s, P, K, sorted, leaf_box, n_leaf, idx, dist2);
 }
 
-}  // namespace
-
 static_assert(F3DGS_KNN_MAX_NEIGHBORS == 16, "the list templates end at 16");
 
 hipError_t launch_knn_neighbors(int P, int K, const float* points, int* idx, float* dist2, char* scratch, bool outward, hipStream_t s) {
@@ -220,4 +218,47 @@ hipError_t launch_label_mode_filter(int P, int K, const int* labels, const float
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+size_t f3dgs_knn_neighbors_scratch_bytes(int P, int K) {
+    (void)K;      // the lists live in registers: the scratch is the front end's (sort buffers, sorted points, leaf boxes)
+    return knn_scratch_bytes((size_t)(P > 0 ? P : 0));
+}
+
+int f3dgs_knn_neighbors(int P, int K, const float* points, int32_t* idx, float* dist2, void* scratch, void* stream) {
+    const char* who = "f3dgs_knn_neighbors";
+    if (P < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
+    if (K < 1 || K > F3DGS_KNN_MAX_NEIGHBORS)
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: K = %d neighbours, 1 .. %d are taken", who, K, F3DGS_KNN_MAX_NEIGHBORS);
+    if (P == 0) return F3DGS_OK;
+    if (P > (1 << 30)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "%s: more than 2^30 points", who);
+    if (!points || !idx || !scratch) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (!aligned16(scratch)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+    HIP_TRY(launch_knn_neighbors(P, K, points, idx, dist2, static_cast<char*>(scratch), options().knn_outward != 0,
+                                 static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_label_mode_filter(int P, int K, const int32_t* labels, const float* weight, const int32_t* idx, const float* dist2,
+                            float max_dist2, int fill, int32_t* labels_out, float* share_out, void* stream) {
+    const char* who = "f3dgs_label_mode_filter";
+    if (P < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: P < 0", who);
+    if (K < 1 || K > F3DGS_KNN_MAX_NEIGHBORS)
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: K = %d neighbours, 1 .. %d are taken", who, K, F3DGS_KNN_MAX_NEIGHBORS);
+    if (!(max_dist2 >= 0.f)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: max_dist2 is negative or NaN", who);
+    if (P == 0) return F3DGS_OK;
+    if (!labels || !idx || !labels_out) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+    if (labels_out == labels) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: labels_out is labels: a Jacobi step cannot run in place", who);
+    if (max_dist2 < INFINITY && !dist2) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "%s: a finite max_dist2 needs dist2", who);
+    HIP_TRY(launch_label_mode_filter(P, K, labels, weight, idx, dist2, max_dist2, fill != 0, labels_out, share_out,
+                                     static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+}  // extern "C"

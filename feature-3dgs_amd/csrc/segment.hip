@@ -289,8 +289,6 @@ struct SegScratch {
     }
 };
 
-}  // namespace
-
 size_t segment_scratch_bytes(int C, int Cout, int Hs, int Ws, int K, bool decoder) {
     size_t b = 0;
     SegScratch::carve(nullptr, C, Cout, Hs * Ws, K, decoder, &b);
@@ -328,4 +326,39 @@ hipError_t launch_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, 
     return hipErrorInvalidValue;
 }
 
+}  // namespace
+
 }  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+size_t f3dgs_segment_scratch_bytes(int C, int Cout, int Hs, int Ws, int K, int has_decoder) {
+    if (C <= 0 || Cout <= 0 || Hs < 0 || Ws < 0 || K <= 0 || (long long)Hs * Ws > (1ll << 30)) return 0;
+    return segment_scratch_bytes(C, Cout, Hs, Ws, K, has_decoder != 0);
+}
+
+int f3dgs_segment(int C, int H, int W, int Cout, int Hs, int Ws, int K, const float* feature_map, const float* weight,
+                  const float* bias, const float* text, int flags, int64_t* labels, float* score, void* scratch, void* stream) {
+    if (C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Hs < 0 || Ws < 0 || K <= 0)
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "segment: bad sizes C=%d H=%d W=%d Cout=%d Hs=%d Ws=%d K=%d", C, H, W, Cout, Hs, Ws, K);
+    const int known = F3DGS_SEGMENT_ROUND_HALF | F3DGS_SEGMENT_TEXT_NORMALIZED;
+    if (flags & ~known) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "segment: unknown flag bits 0x%x", flags & ~known);
+    if ((weight == nullptr) != (bias == nullptr)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "segment: weight and bias go together");
+    if (!weight && Cout != C)
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "segment: without a decoder the text has C = %d channels, got %d", C, Cout);
+    if (K > F3DGS_SEGMENT_MAX_TEXTS) return report_errorf(F3DGS_ERR_UNSUPPORTED, "segment: K=%d beyond the limit of %d text rows", K, F3DGS_SEGMENT_MAX_TEXTS);
+    if (weight && (!feature_l1_decoder_supported(C) || Cout % 32 != 0))
+        return report_errorf(F3DGS_ERR_UNSUPPORTED, "segment: decoder %d -> %d: supported are input widths 32, 64, 128 and outputs that are multiples of 32", C, Cout);
+    if ((long long)Hs * Ws > (1ll << 30) || (long long)H * W > (1ll << 28)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "segment: too large");
+    if (Hs == 0 || Ws == 0) return F3DGS_OK;
+    const bool text_normalized = (flags & F3DGS_SEGMENT_TEXT_NORMALIZED) != 0;
+    if (!feature_map || !text || !labels) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "segment: null pointer");
+    if (!scratch && (weight || !text_normalized)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "segment: scratch is null");
+    HIP_TRY(launch_segment(C, H, W, Cout, Hs, Ws, K, feature_map, weight, bias, text, (flags & F3DGS_SEGMENT_ROUND_HALF) != 0,
+                           text_normalized, labels, score, static_cast<char*>(scratch), static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+}  // extern "C"

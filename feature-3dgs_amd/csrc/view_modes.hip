@@ -266,8 +266,6 @@ inline unsigned tiles_of(int H, int W, int* tiles_x) {
     return (unsigned)((size_t)*tiles_x * ((H + VT - 1) / VT));
 }
 
-}  // namespace
-
 hipError_t launch_view_normals(int H, int W, const float* depth, const float* proj, const double* inv, float* out, bool chw, bool half,
                                hipStream_t s) {
     int tx;
@@ -312,4 +310,84 @@ hipError_t launch_view_bytes(size_t HW, const float* image, unsigned char* out, 
     return hipGetLastError();
 }
 
+// nullptr if the frame is served, else the reason
+const char* view_unsupported(int H, int W, bool unprojects) {
+    if ((long long)H * W > (1ll << 30)) return "view: %d x %d pixels: the frame is too large";
+    if (unprojects && H > 0 && W > 0 && (H == 1 || W == 1))
+        return "view: %d x %d pixels: normals need at least 2 rows and 2 columns (x / (W - 1), y / (H - 1))";
+    return nullptr;
+}
+
+}  // namespace
+
 }  // namespace f3dgs
+
+using namespace f3dgs;
+
+extern "C" {
+
+int f3dgs_view_normals(int H, int W, const float* depth, const float* proj, const double* inv_full_proj, float* out, int flags,
+                       void* stream) {
+    if (H < 0 || W < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_normals: bad sizes H=%d W=%d", H, W);
+    const int known = F3DGS_VIEW_NORMALS_CHW | F3DGS_VIEW_NORMALS_HALF;
+    if (flags & ~known) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_normals: unknown flag bits 0x%x", flags & ~known);
+    if (const char* why = view_unsupported(H, W, true)) return report_errorf(F3DGS_ERR_UNSUPPORTED, why, H, W);
+    if (H == 0 || W == 0) return F3DGS_OK;
+    if (!depth || !proj || !inv_full_proj || !out) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_normals: null pointer");
+    HIP_TRY(launch_view_normals(H, W, depth, proj, inv_full_proj, out, (flags & F3DGS_VIEW_NORMALS_CHW) != 0,
+                                (flags & F3DGS_VIEW_NORMALS_HALF) != 0, static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_view_gradient(int Cn, int H, int W, const float* image, float* out, float* minmax, void* stream) {
+    if (Cn < 1 || H < 0 || W < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_gradient: bad sizes Cn=%d H=%d W=%d", Cn, H, W);
+    if (const char* why = view_unsupported(H, W, false)) return report_errorf(F3DGS_ERR_UNSUPPORTED, why, H, W);
+    if (H == 0 || W == 0) return F3DGS_OK;
+    if (!image || !out) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_gradient: null pointer");
+    HIP_TRY(launch_view_gradient(Cn, H, W, image, out, minmax, static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_view_curvature(int H, int W, const float* depth, const float* proj, const double* inv_full_proj, float* out, float* minmax,
+                         void* stream) {
+    if (H < 0 || W < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_curvature: bad sizes H=%d W=%d", H, W);
+    if (const char* why = view_unsupported(H, W, true)) return report_errorf(F3DGS_ERR_UNSUPPORTED, why, H, W);
+    if (H == 0 || W == 0) return F3DGS_OK;
+    if (!depth || !proj || !inv_full_proj || !out) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_curvature: null pointer");
+    HIP_TRY(launch_view_curvature(H, W, depth, proj, inv_full_proj, out, minmax, static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_view_minmax(long long n, const float* field, float* minmax, void* stream) {
+    if (n < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_minmax: n = %lld", n);
+    if (n > (1ll << 30)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "view_minmax: %lld values: the field is too large", n);
+    if (n == 0) return F3DGS_OK;
+    if (!field || !minmax) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_minmax: null pointer");
+    HIP_TRY(launch_view_minmax((size_t)n, field, minmax, static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_view_palette(long long HW, const float* field, const float* minmax, const float* lut, int L, int mode, float* out_float,
+                       uint8_t* out_u8, void* stream) {
+    if (HW < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_palette: HW = %lld", HW);
+    if (mode != F3DGS_VIEW_PALETTE_MINMAX && mode != F3DGS_VIEW_PALETTE_MAX)
+        return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_palette: unknown mode %d", mode);
+    if (HW > (1ll << 30)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "view_palette: %lld pixels: the frame is too large", HW);
+    if (L < 2 || L > F3DGS_VIEW_PALETTE_MAX_ENTRIES)
+        return report_errorf(F3DGS_ERR_UNSUPPORTED, "view_palette: a palette of %d entries: supported are 2 to %d", L, F3DGS_VIEW_PALETTE_MAX_ENTRIES);
+    if (HW == 0) return F3DGS_OK;
+    if (!field || !minmax || !lut || (!out_float && !out_u8)) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_palette: null pointer");
+    HIP_TRY(launch_view_palette((size_t)HW, field, minmax, lut, L, mode, out_float, out_u8, static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+int f3dgs_view_bytes(long long HW, const float* image, uint8_t* out_u8, void* stream) {
+    if (HW < 0) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_bytes: HW = %lld", HW);
+    if (HW > (1ll << 30)) return report_errorf(F3DGS_ERR_UNSUPPORTED, "view_bytes: %lld pixels: the frame is too large", HW);
+    if (HW == 0) return F3DGS_OK;
+    if (!image || !out_u8) return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "view_bytes: null pointer");
+    HIP_TRY(launch_view_bytes((size_t)HW, image, out_u8, static_cast<hipStream_t>(stream)));
+    return F3DGS_OK;
+}
+
+}  // extern "C"
