@@ -6,6 +6,8 @@
 //   label_mode_filter(labels, weight, idx, dist2, max_dist2, fill, labels_out, share_out): one step of f3dgs_label_mode_filter
 //   knn_components(idx, dist2, max_dist2, labels, mutual, dense) -> (root, size, comp, comp_root, n_comp, status): f3dgs_knn_components
 //   component_filter(labels, root, size, min_size, largest, num_labels, labels_out): f3dgs_component_filter
+//   radius_count(points, radius2, labels, cap) -> count (P,) int32: f3dgs_radius_count
+//   knn_outliers(idx, dist2, labels, num_groups, ratio) -> (score (P,) float32, keep (P,) bool, stats (G, 4) float64): f3dgs_knn_outliers
 //   group_stats(groups, xyz, G, weight, features, want) -> (count, mass, centroid, cov, aabb, feature_mean), each or None: f3dgs_group_stats
 //   group_merge(groups, idx, dist2, max_dist2, mutual, feature_mean, min_cos, out) -> (groups_out, group_root, status): f3dgs_group_merge
 //   transform_gaussians(groups, quat, scale, translation, pivot, xyz, rotations, scales, linear, cov3d, sh_rest, rows, inplace)
@@ -150,6 +152,54 @@ void component_filter(const c10::optional<torch::Tensor>& labels, const torch::T
                                           size.data_ptr<int32_t>(), min_size, largest ? 1 : 0, num_labels, labels_out.data_ptr<int32_t>(),
                                           largest ? scratch.data_ptr() : nullptr, current_stream(root));
     if (rc != F3DGS_OK) throw std::runtime_error(std::string("component_filter: ") + f3dgs_last_error());
+}
+
+// f3dgs_radius_count: count (P) int32; labels: contiguous int32 (P) or None; cap: 0 = no cap
+torch::Tensor radius_count(const torch::Tensor& points, double radius2, const c10::optional<torch::Tensor>& labels, int cap) {
+    TORCH_CHECK(points.is_cuda(), "points must live on a HIP device: the radius count has no CPU path");
+    TORCH_CHECK(points.dim() == 2 && points.size(1) == 3, "points must have dimensions (num_points, 3)");
+    TORCH_CHECK(points.scalar_type() == torch::kFloat32, "points must be float32");
+    TORCH_CHECK(points.size(0) <= (1ll << 30), "too many points");
+    TORCH_CHECK(radius2 >= 0.0, "radius2 = ", radius2, ": a squared radius >= 0 expected");
+    TORCH_CHECK(cap >= 0, "cap = ", cap, ": 0 (no cap) or a positive count expected");
+    const long long P = points.size(0);
+    if (labels) check_node_array(*labels, P, points.device(), "labels");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(points.device());
+    auto pts = points.contiguous();
+    torch::Tensor count = torch::empty({P}, points.options().dtype(torch::kInt32));
+    if (P == 0) return count;
+    torch::Tensor scratch = torch::empty({(long long)f3dgs_radius_count_scratch_bytes((int)P)}, points.options().dtype(torch::kByte));
+    const int rc = f3dgs_radius_count((int)P, pts.data_ptr<float>(), (float)radius2, labels ? labels->data_ptr<int32_t>() : nullptr, cap,
+                                      count.data_ptr<int32_t>(), scratch.data_ptr(), current_stream(points));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("radius_count: ") + f3dgs_last_error());
+    return count;
+}
+
+// f3dgs_knn_outliers: (score (P) float32, keep (P) bool, stats (num_groups, 4) float64).  Nothing is read back.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> knn_outliers(const torch::Tensor& idx, const torch::Tensor& dist2,
+                                                                     const c10::optional<torch::Tensor>& labels, int num_groups,
+                                                                     double ratio) {
+    TORCH_CHECK(idx.is_cuda(), "idx must live on a HIP device: the outlier scores have no CPU path");
+    TORCH_CHECK(idx.dim() == 2 && idx.scalar_type() == torch::kInt32 && idx.is_contiguous(), "idx: contiguous int32 (P, K) expected");
+    TORCH_CHECK(idx.size(0) <= (1ll << 30), "too many points");
+    const long long P = idx.size(0);
+    const int K = (int)idx.size(1);
+    TORCH_CHECK(dist2.sizes() == idx.sizes() && dist2.scalar_type() == torch::kFloat32 && dist2.device() == idx.device() &&
+                    dist2.is_contiguous(), "dist2: contiguous float32 (P, K) on the lists' device expected");
+    if (labels) check_node_array(*labels, P, idx.device(), "labels");
+    TORCH_CHECK(num_groups >= 1 && (labels || num_groups == 1), "num_groups = ", num_groups, ": >= 1, and 1 without labels");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(idx.device());
+    torch::Tensor score = torch::empty({P}, dist2.options());
+    torch::Tensor keep = torch::empty({P}, idx.options().dtype(torch::kBool));
+    torch::Tensor stats = torch::empty({(long long)num_groups, 4}, idx.options().dtype(torch::kFloat64));
+    torch::Tensor scratch = torch::empty({(long long)f3dgs_knn_outliers_scratch_bytes(num_groups)}, idx.options().dtype(torch::kByte));
+    // (an empty tensor has no address: with P == 0 nothing is read or written through these)
+    const int rc = f3dgs_knn_outliers((int)P, K, P > 0 ? idx.data_ptr<int32_t>() : nullptr, P > 0 ? dist2.data_ptr<float>() : nullptr,
+                                      (labels && P > 0) ? labels->data_ptr<int32_t>() : nullptr, num_groups, (float)ratio,
+                                      P > 0 ? score.data_ptr<float>() : nullptr, stats.data_ptr<double>(),
+                                      P > 0 ? static_cast<uint8_t*>(keep.data_ptr()) : nullptr, scratch.data_ptr(), current_stream(idx));
+    if (rc != F3DGS_OK) throw std::runtime_error(std::string("knn_outliers: ") + f3dgs_last_error());
+    return {score, keep, stats};
 }
 
 // f3dgs_group_stats: `want` names the outputs (GROUP_COUNT ... GROUP_FEATURE_MEAN); the others come back as None.  count (G) int32,
@@ -414,6 +464,8 @@ PYBIND11_MODULE(_C, m) {
     m.def("label_mode_filter", &label_mode_filter);
     m.def("knn_components", &knn_components);
     m.def("component_filter", &component_filter);
+    m.def("radius_count", &radius_count);
+    m.def("knn_outliers", &knn_outliers);
     m.def("group_stats", &group_stats);
     m.def("group_merge", &group_merge);
     m.def("transform_gaussians", &transform_gaussians);

@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "leaf_walk.h"
 
 namespace f3dgs {
 
@@ -29,18 +30,7 @@ namespace {
 
 constexpr int LEAF = KNN_LEAF;
 constexpr int NO_INDEX = 0x7FFFFFFF;      // an empty slot: behind every real index at the distance +inf
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;      // false for a NaN
-}
-
-// the squared distance from (x, y, z) to the box: the operations of a candidate's distance, on the nearest face
-__device__ __forceinline__ float box_bound(const KnnBox& b, float x, float y, float z) {
-    const float dx = fmaxf(fmaxf(b.lo[0] - x, x - b.hi[0]), 0.f);
-    const float dy = fmaxf(fmaxf(b.lo[1] - y, y - b.hi[1]), 0.f);
-    const float dz = fmaxf(fmaxf(b.lo[2] - z, z - b.hi[2]), 0.f);
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
+// (finite3 and box_bound: leaf_walk.h, shared with outliers.hip)
 
 // A lane's best (distance, index) pairs in LS slots, ascending in that order.  Every index below is a compile-time constant after
 // unrolling: the list lives in registers (a runtime-indexed private array would go to scratch memory).

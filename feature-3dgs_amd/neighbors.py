@@ -1,4 +1,5 @@
-"""Neighbourhoods of the Gaussians in 3D: K-nearest-neighbour lists with indices, and a mode filter of per-Gaussian labels.
+"""Neighbourhoods of the Gaussians in 3D: K-nearest-neighbour lists with indices, a mode filter of per-Gaussian labels, connected
+components over the lists, and the two density tests: radius counts and statistical outlier removal.
 
 LabelLifter, InstanceLifter and edit.selection_mask decide every Gaussian from 2D evidence alone.  This module looks at a
 Gaussian's neighbours (csrc/neighbors.hip behind include/f3dgs.h: f3dgs_knn_neighbors, f3dgs_label_mode_filter):
@@ -24,6 +25,21 @@ a selection exists:
     mask = neighbors.clean_selection(lifter.select(cls), idx)
     mask = neighbors.keep_largest(mask, idx)
     ids = neighbors.split_labels(instance_lifter.labels(), idx, dist2=dist2, max_dist=0.1).comp
+
+A component filter removes a floater only where it is a component of its own.  One that hangs on its object by a thin bridge, or
+a sparse halo around a dense body, is one component with the body; the two DENSITY tests catch both (csrc/outliers.hip:
+f3dgs_radius_count, f3dgs_knn_outliers):
+
+    radius_count                 per point the number of other points within a radius (of the same label), exact, on request
+                                 saturated at a cap; no lists: a fixed-radius walk of the search's leaves
+    outlier_scores               per point the mean distance to its list's neighbours, per group the mean and the standard
+                                 deviation of that score, and keep = score <= mean + ratio * std
+    remove_statistical_outliers  labels, a bool mask or nothing in, the same without the statistical outliers out
+    remove_radius_outliers       the same with "fewer than min_neighbors points within radius"
+
+    keep = neighbors.remove_statistical_outliers(None, gaussians.get_xyz.detach(), k=8, ratio=2.0)
+    densify.prune_points(model, ~keep)
+    mask = neighbors.remove_radius_outliers(mask, gaussians.get_xyz.detach(), radius=0.05, min_neighbors=4)
 
 HIP only; no CPU fallback.  Nothing is read back to the host.
 """
@@ -241,5 +257,122 @@ def split_labels(labels, idx, dist2=None, max_dist=None, mutual=False):
     return SplitLabels(comp.long(), n_comp.long(), comp_label)
 
 
+# ---- density: radius counts and statistical outlier removal --------------------------------------------------------------------
+
+Outliers = collections.namedtuple("Outliers", ["score", "keep", "stats"])
+
+
+def _points(points, name="points"):
+    _need_device(points, name)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{name}: a float32 (P, 3) tensor expected, got {_describe(points)}")
+    return points.detach()
+
+
+def _node_labels(labels, P, dev, name="labels"):
+    """(P,) int32 / int64 labels on `dev` as the kernels take them: int32, contiguous, every negative value -1"""
+    if not torch.is_tensor(labels) or labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64) or labels.shape[0] != P \
+            or labels.device != dev:
+        raise ValueError(f"{name}: an int32 or int64 ({P},) tensor on {dev} expected, got {_describe(labels)}")
+    return labels.detach().clamp_min(-1).to(torch.int32).contiguous()
+
+
+def _count(value, name, least):
+    if not isinstance(value, int) or isinstance(value, bool) or not least <= value < 2**31:
+        raise ValueError(f"{name} = {value!r}: an integer >= {least} expected")
+    return value
+
+
+def radius_count(points, radius, labels=None, cap=None):
+    """The number of other points within `radius` of every point.  points: (P, 3) float32 on the device.  radius: a number >= 0
+    (inf allowed), squared in float32; point j is within it iff ((dx*dx) + (dy*dy)) + (dz*dz) <= radius^2 in float32, knn's
+    distance.  labels: (P,) int32 or int64 or None: only points of the same non-negative label are counted, and a point with a
+    negative label gets 0.  cap: None or an integer >= 1, the result is min(count, cap) (the walk of a point ends there: ask for no
+    more than the decision needs).  Self is excluded by index: duplicates are counted.  A point with a NaN or infinite coordinate has
+    count 0 and is counted by nobody.  Returns (P,) int32, a function of the inputs alone."""
+    pts = _points(points)
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or math.isnan(radius) or radius < 0:
+        raise ValueError(f"radius = {radius!r}: a number >= 0 expected")
+    r = torch.tensor(float(radius), dtype=torch.float32)
+    radius2 = float(r * r)
+    labels32 = None if labels is None else _node_labels(labels, pts.shape[0], pts.device)
+    limit = 0 if cap is None else _count(cap, "cap", 1)
+    with torch.no_grad():
+        return _C.radius_count(pts, radius2, labels32, limit)
+
+
+def _scores(idx, dist2, labels32, num_groups, ratio):
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not math.isfinite(ratio) or ratio < 0:
+        raise ValueError(f"ratio = {ratio!r}: a finite number >= 0 expected")
+    with torch.no_grad():
+        return Outliers(*_C.knn_outliers(idx.contiguous(), dist2.detach().contiguous(), labels32, num_groups, float(ratio)))
+
+
+def outlier_scores(idx, dist2, labels=None, num_labels=None, ratio=2.0):
+    """Statistical outlier scores over knn's lists.  idx (P, K) int32, dist2 (P, K) float32 (any integers are allowed in idx).
+    labels: (P,) int32 or int64 with num_labels, or None (one group).  Gaussian i is a member iff 0 <= labels[i] < num_labels; a
+    slot of its row counts iff its entry j is in 0 .. P-1, is not i, carries i's label and its dist2 is < inf.
+
+    Returns Outliers(score, keep, stats): score (P,) float32, the mean of sqrt(dist2) over the counting slots, formed in float64 and
+    rounded once (+inf for a Gaussian that is no member or has no such slot); stats (G, 4) float64 on the device, never read
+    here: per group {n, mean, std, threshold} over its members with a finite score, std the N - 1 form (0 for n < 2), threshold =
+    mean + ratio * std; keep (P,) bool: score < inf and score <= threshold of its group."""
+    _need_device(idx, "idx")
+    P = idx.shape[0] if idx.dim() else -1
+    _check_lists(idx, dist2, P, idx.device)
+    if dist2 is None:
+        raise ValueError("dist2: the squared distances of knn are needed, got None")
+    if labels is None:
+        if num_labels is not None:
+            raise ValueError(f"num_labels = {num_labels!r} without labels: one group, None expected")
+        return _scores(idx, dist2, None, 1, ratio)
+    labels32 = _node_labels(labels, P, idx.device)
+    return _scores(idx, dist2, labels32, _count(num_labels, "num_labels", 1), ratio)
+
+
+def _density_input(labels_or_mask, xyz, num_labels, need_num_labels):
+    """(xyz, labels32 or None, num_groups, kind) of labels, a bool mask or None over the points xyz"""
+    pts = _points(xyz, "xyz")
+    P, dev = pts.shape[0], pts.device
+    if labels_or_mask is None:
+        return pts, None, 1, "none"
+    if torch.is_tensor(labels_or_mask) and labels_or_mask.dtype == torch.bool:
+        if labels_or_mask.dim() != 1 or labels_or_mask.shape[0] != P or labels_or_mask.device != dev:
+            raise ValueError(f"mask: a bool ({P},) tensor on {dev} expected, got {_describe(labels_or_mask)}")
+        return pts, labels_or_mask.to(torch.int32) - 1, 1, "mask"                 # selected: label 0, unselected: -1
+    labels32 = _node_labels(labels_or_mask, P, dev)
+    if need_num_labels and (not isinstance(num_labels, int) or isinstance(num_labels, bool) or not 1 <= num_labels < 2**31):
+        raise ValueError(f"num_labels = {num_labels!r}: the statistics of labels need the number of labels (a lifter's class count or "
+                         f"max_instances), an integer >= 1")
+    return pts, labels32, num_labels, "labels"
+
+
+def _density_result(keep, labels32, kind):
+    if kind == "labels":
+        return torch.where(keep, labels32, torch.full((), -1, dtype=torch.int32, device=keep.device)).long()
+    return keep
+
+
+def remove_statistical_outliers(labels_or_mask, xyz, k=8, ratio=2.0, num_labels=None):
+    """Statistical outlier removal: knn(xyz, k), outlier_scores per label, and what is not kept goes.  labels_or_mask: (P,) int32 /
+    int64 labels with num_labels (negative = unlabelled; every label has its own mean and deviation, a label >= num_labels is
+    dropped), a bool `mask` of edit.apply_edit (selected = one group, as drop_small treats it) or None (all points one group).
+    Returns the labels as int64 with -1 for the outliers, the mask as bool, or - for None - the bool keep over all points."""
+    pts, labels32, groups, kind = _density_input(labels_or_mask, xyz, num_labels, True)
+    idx, dist2 = knn(pts, k)
+    return _density_result(_scores(idx, dist2, labels32, groups, ratio).keep, labels32, kind)
+
+
+def remove_radius_outliers(labels_or_mask, xyz, radius, min_neighbors):
+    """Radius outlier removal: what has fewer than min_neighbors other points (of its label) within `radius` goes -
+    radius_count(cap=min_neighbors) >= min_neighbors.  labels_or_mask and the result: as for remove_statistical_outliers (labels
+    need no num_labels here)."""
+    pts, labels32, _, kind = _density_input(labels_or_mask, xyz, None, False)
+    limit = _count(min_neighbors, "min_neighbors", 1)
+    keep = radius_count(pts, radius, labels32, cap=limit) >= limit
+    return _density_result(keep, labels32, kind)
+
+
 __all__ = ["MAX_NEIGHBORS", "knn", "mode_filter", "smooth_labels", "clean_selection", "Components", "SplitLabels", "components",
-           "drop_small", "keep_largest", "split_labels"]
+           "drop_small", "keep_largest", "split_labels", "Outliers", "radius_count", "outlier_scores", "remove_statistical_outliers",
+           "remove_radius_outliers"]

@@ -1090,6 +1090,57 @@ int f3dgs_debug_knn_components_shape(int P, int K, const int32_t* idx, const flo
                                      int32_t* status /* device */, void* stream /* hipStream_t */);
 
 /*
+ * The two density tests of a point cloud (ABI 3.25; no counterpart in the reference): "fewer than n points within r" and "mean
+ * neighbour distance above mean + ratio * std" - what removes a floater that hangs on its object by a thin bridge, or a sparse
+ * halo around a dense body, which are ONE component for f3dgs_component_filter.
+ *
+ * f3dgs_radius_count.  points (P, 3) float32, labels (P) int32 or NULL, count (P) int32: device pointers.  count[i] is the number
+ * of points j != i with dist2(i, j) <= radius2, where dist2 = ((dx*dx) + (dy*dy)) + (dz*dz) and dx = p_j - p_i in float32, one
+ * rounding per operation: f3dgs_knn_neighbors' distance, so count[i] >= k says what "the k-th entry of row i is <= radius2" says.
+ *   labels   j is counted only if labels[j] == labels[i] >= 0 (f3dgs_knn_components' equal-label rule); a query with a negative
+ *            label gets 0.  Any int32 may stand there.
+ *   finite   a point with a NaN or infinite coordinate has count 0 and is counted by nobody.  A pair of finite points whose distance
+ *            overflows float32 is counted only by radius2 = +inf, which is legal and counts every other finite point (of the label).
+ *   cap      cap > 0 saturates the result: count[i] = min(true count, cap) - the walk of a lane ends at its cap, which is what
+ *            "at least n neighbours" needs; cap == 0: no cap.
+ *   self     excluded by index, not by distance: a duplicate of point i is counted, so radius2 = 0 counts the duplicates.
+ * The result is an integer function of the inputs alone (not of the sort order, the walk order or the lanes).
+ * `scratch` = f3dgs_radius_count_scratch_bytes(P) bytes of device memory, 16-byte aligned (the search's front end and P labels in
+ * sorted order).  P == 0 is a no-op.  P < 0, a negative or NaN radius2, cap < 0, a NULL points / count / scratch, a misaligned
+ * scratch: F3DGS_ERR_INVALID_ARGUMENT before any device work; P > 2^30: F3DGS_ERR_UNSUPPORTED.  No host read, no allocation, no
+ * memset; every launch goes to `stream`: capturable.
+ *
+ * f3dgs_knn_outliers: statistical outlier removal over the lists of f3dgs_knn_neighbors.  idx (P, K) int32 - the caller's: any
+ * integers, every entry is bounds-checked -, dist2 (P, K) float32, labels (P) int32 or NULL, score (P) float32, stats
+ * (num_groups x 4) float64, keep (P) bytes: device pointers.  1 <= K <= F3DGS_KNN_MAX_NEIGHBORS, num_groups >= 1, ratio finite
+ * and >= 0.
+ *   Group      g(i) = labels ? labels[i] : 0 (without labels num_groups must be 1).  Point i is a MEMBER iff 0 <= g(i) < num_groups.
+ *   Valid slot slot s of row i is valid iff j = idx[i, s] satisfies 0 <= j < P, j != i and g(j) == g(i), and dist2[i, s] < +inf (a
+ *              NaN is not valid; FLT_MAX beside idx -1, the search's empty slot, fails the index test): f3dgs_knn_components' edge.
+ *   score[i]   (float)(sum of sqrt((double)dist2[i, s]) over the valid slots in slot order / their number): the mean neighbour
+ *              distance in fp64 with the correctly rounded square root, rounded once.  +inf for a point that is no member and for
+ *              a member without a valid slot.  (A negative dist2 is not a distance: its score is NaN, which counts as not finite.)
+ *   stats[g]   {n, mean, std, threshold} over the members of g with a finite score: n their number, mean = sum score / n, std =
+ *              sqrt(sum (score - mean)^2 / (n - 1)) in a second pass about the device's own fp64 mean (the N - 1 form of Open3D and
+ *              PCL; 0 for n < 2), threshold = mean + ratio * std.  A group without such a member: four zeros.
+ *   keep[i]    1 iff score[i] < +inf and (double)score[i] <= threshold[g(i)], else 0.
+ * Every sum is fp64 on the device; the group sums meet in one atomic per distinct group and wave, in a varying order: n, score
+ * and - away from a threshold - keep are functions of the inputs alone, mean, std and threshold to the error of an fp64 sum.
+ * `scratch` = f3dgs_knn_outliers_scratch_bytes(num_groups) bytes of device memory, 8-byte aligned.  With P == 0 stats is zeroed.
+ * P < 0, K or num_groups out of range, num_groups != 1 without labels, a negative or non-finite ratio, a NULL stats / scratch,
+ * with P > 0 a NULL idx / dist2 / score / keep, a misaligned scratch: F3DGS_ERR_INVALID_ARGUMENT before any device work; P > 2^30:
+ * F3DGS_ERR_UNSUPPORTED.  Four launches (clear; scores and first sums; second sums; thresholds and keep), no workgroup waits for
+ * another, no host read, no allocation: capturable.
+ */
+size_t f3dgs_radius_count_scratch_bytes(int P);
+int f3dgs_radius_count(int P, const float* points, float radius2, const int32_t* labels /* or NULL */, int cap, int32_t* count,
+                       void* scratch, void* stream /* hipStream_t */);
+size_t f3dgs_knn_outliers_scratch_bytes(int num_groups);
+int f3dgs_knn_outliers(int P, int K, const int32_t* idx, const float* dist2, const int32_t* labels /* or NULL */, int num_groups,
+                       float ratio, float* score /* P */, double* stats /* num_groups x 4 */, uint8_t* keep /* P */, void* scratch,
+                       void* stream /* hipStream_t */);
+
+/*
  * Statistics of the Gaussians per group id (ABI 3.20; no counterpart in the reference): what the integers of the label vote, the
  * instance association, the mode filter and the components say about a class, an instance or a component AS A WHOLE.
  *
