@@ -290,6 +290,7 @@ const OptionDesc kOptions[] = {
     {"bwd_bf16_max_ratio", "F3DGS_BWD_BF16_MAX_RATIO", &Options::bwd_bf16_max_ratio, 16},
     {"bwd_wide8", "F3DGS_BWD_WIDE8", &Options::bwd_wide8, 1},
     {"fwd_wide", "F3DGS_FWD_WIDE", &Options::fwd_wide, 1},
+    {"fwd_round", "F3DGS_FWD_ROUND", &Options::fwd_round, 64},
     {"fwd_solo", "F3DGS_FWD_SOLO", &Options::fwd_solo, 1},
     {"sort_onesweep", "F3DGS_SORT_ONESWEEP", &Options::sort_onesweep, 0},
     {"depth_sort_buckets", "F3DGS_DEPTH_SORT_BUCKETS", &Options::depth_sort_buckets, -1},
@@ -910,6 +911,7 @@ int f3dgs_debug_read(const char* what, int P, int C, int R, int width, int heigh
     else if (w == "ranges") { src = img.ranges; bytes = tiles * 8; }
     else if (w == "final_T") { src = img.final_T; bytes = HW * 4; }
     else if (w == "n_contrib") { src = img.n_contrib; bytes = HW * 4; }
+    else if (w == "tile_len") { src = img.tile_len; bytes = tiles * 4; }
     else return report_errorf(F3DGS_ERR_INVALID_ARGUMENT, "unknown debug item '%s'", what);
     if (bytes > dst_bytes) bytes = dst_bytes;
     if (bytes) {

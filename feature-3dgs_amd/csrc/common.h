@@ -299,6 +299,7 @@ struct Options {
     int bwd_wide8;       // pixel-lane blend backward, bf16 shape: later channel windows of up to 128 channels on eight waves per tile where more than 64 channels remain (default 1)
     int bwd_pl;          // blend backward: pixel-lane formulation with all sums on the matrix pipe: 1 always, 0 never, -1 (default) for C > 0 (C > 4 with bwd_bf16 = 0); needs feature_mfma
     int fwd_wide;        // blend forward: 128-channel windows where more than 64 channels remain (default 1)
+    int fwd_round;       // blend forward, 16- and 32-channel matrix shapes: list positions tested per round, 64 (default; hits queued in a ring, blended in full chunks of 32) or 32
     int fwd_solo;        // blend forward, one quadrant per wave: one 64-thread workgroup per quadrant (default 1; the waves never synchronise)
     int depth_sort_buckets;   // depth sort of more than SMALL_SORT_MAX Gaussians: one bucket pass and an in-LDS sort per bucket instead of the LSD passes: 1 always, 0 never, -1 (default) for DEPTH_BUCKET_AUTO_ABOVE < P <= DEPTH_BUCKET_AUTO_UPTO
     int sort_onesweep;   // 1: single-pass radix passes with decoupled look-back (measured slower on MI355X; default 0)

@@ -268,17 +268,30 @@ __global__ void __launch_bounds__(256 / PPL) render_forward_kernel(FwdArgs a) {
 // one v_permlane32_swap; B[k][n] = feature n of instance j+k, one ds_read_b32 per lane.
 // (FwdEntry - one staged, compacted list entry - and the group step of the blend loop live in fwd_group.h)
 
-template <int CH, int CHK>
+// QN: entries the staging area holds.  QN = CHK: one compacted chunk at a time (32-candidate rounds).  QN = 3 CHK: a ring of
+// compacted entries fed by 64-candidate rounds (31 left over + 64 new at the most); chunks are taken off it 32 at a time, so a
+// chunk starts at 0, CHK or 2 CHK and never wraps.  The feature-row image stays one chunk of CHK rows either way.
+template <int CH, int CHK, int QN>
 struct FwdChunkMF {
-    FwdEntry ent[CHK];
+    FwdEntry ent[QN];
     // epilogue transpose tile: [channel][65] for all 64 pixels at once.  ([channel][33], one half of the pixels at a time,
     // would cut the wave's LDS from 9.6 to 5.6 KB - and a fifth wave per SIMD fits the registers with 3-4 spilled - but the
     // half-width output stores cost more than the occupancy buys: c3 forward 0.363 -> 0.378 ms at four waves, 0.377 at five;
     // the code path stays for the record, TS = 33 selects it.)
     static constexpr int TS = 65;
-    static constexpr int FT = (CHK * CH > 32 * TS) ? CHK * CH : 32 * TS;
-    float feat[FT];        // row-major [instance][channel]; reused as the epilogue transpose tile
+    // QN = CHK: the tile reuses the feature rows.  With the ring the entries are dead as well by the time of the epilogue: the
+    // tile lies over the whole slice (from its first byte), and the slice is the larger of the two images.
+    static constexpr bool RING = QN > CHK;
+    static constexpr int ENT_DW = QN * (int)(sizeof(FwdEntry) / sizeof(float));
+    static constexpr int TILE_DW = RING ? 32 * TS - ENT_DW : 32 * TS;
+    static constexpr int FT = (CHK * CH > TILE_DW) ? CHK * CH : TILE_DW;
+    float feat[FT];        // row-major [instance][channel]; (QN = CHK) reused as the epilogue transpose tile
+    __device__ float* tile() { return RING ? reinterpret_cast<float*>(this) : feat; }
 };
+static_assert(sizeof(FwdChunkMF<32, 32, 32>) == 9856 && sizeof(FwdChunkMF<32, 32, 96>) == 8704 && sizeof(FwdChunkMF<16, 32, 96>) == 8320,
+              "the blend forward's LDS slice per wave");
+// four waves per SIMD = 16 slices per CU in 160 KB of LDS
+static_assert(16 * sizeof(FwdChunkMF<32, 32, 96>) <= 160 * 1024 && 16 * sizeof(FwdChunkMF<16, 32, 96>) <= 160 * 1024, "LDS of the w4 shapes");
 
 // The next chunk's ids and splat records are prefetched into registers while the current chunk is blended.
 // (Fetching the B operand straight from global memory, prefetched two groups ahead, was measured slower
@@ -288,8 +301,17 @@ struct FwdChunkMF {
 // CH = 16 (windows of 5..16 channels): the 32-column B operand has room to spare, so on the base launch columns 16..19 carry
 // the splat's colour and depth (CDB: read straight out of the staged entry) and their four multiply-adds per (pixel, entry)
 // leave the vector pipe - the pipe this kernel is bound by.
-template <int CH, int PPL, int CHK, int GI, bool BASE>
+// RND: list positions tested per round.  RND = CHK (32): every round forms one chunk of its hits - lanes 32..63 sit out the
+// footprint test and the compaction, and a chunk is two thirds full at c3.  RND = 64 (one quadrant per wave only): all 64 lanes
+// test a candidate, the hits are appended to the ring (FwdChunkMF) and a chunk is blended whenever CHK entries are queued: one
+// round prologue per 64 list positions, full chunks, padding only when the ring drains at the end of the list.  The entries and
+// their order are the same, so are the results (an entry pair of the matrix instruction is a chain of two multiply-adds: how the
+// list is cut into pairs does not show).
+template <int CH, int PPL, int CHK, int GI, bool BASE, int RND>
 __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
+    static_assert(RND == CHK || (RND == 64 && PPL == 1 && CHK == 32), "64-candidate rounds: one quadrant per wave, chunks of 32");
+    constexpr int QN = RND == CHK ? CHK : CHK + RND;      // ring: CHK - 1 left over + RND new, in whole chunks
+    using Chunk = FwdChunkMF<CH, CHK, QN>;
     constexpr int NW = 4 / PPL;
     constexpr int NB = (CH + 31) / 32;
     constexpr bool CDB = BASE && CH == 16;
@@ -302,7 +324,7 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
     const uint32_t vb = xcd_remap(blockIdx.x, gridDim.x);
     const bool solo = PPL == 1 && a.solo;
     const int wave = solo ? (int)(vb & 3u) : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    FwdChunkMF<CH, CHK>& ck = reinterpret_cast<FwdChunkMF<CH, CHK>*>(smem)[(NW > 1 && !solo) ? wave : 0];
+    Chunk& ck = reinterpret_cast<Chunk*>(smem)[(NW > 1 && !solo) ? wave : 0];
 
     const uint32_t tile = band_perm(solo ? vb >> 2 : vb, (uint32_t)(a.gx * a.gy), a.band_b0, a.band_tb);
     const int tx = tile % a.gx, ty = tile / a.gx;
@@ -370,41 +392,46 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
     // CH = 16: where this lane's B column lives (dwords from the start of the chunk image, per staged entry): channels 0..15
     // in the feature rows; columns 16..19 = colour and depth inside the 12-dword entry; the remaining columns re-read those
     // (finite values; their sums are never looked at)
-    int b_stride = 0, b_off = 0;
+    int b_stride = 0, b_off = 0, b_adj = 0;
     if constexpr (CH == 16) {
         const int n = lane & 31;
-        using Chunk = FwdChunkMF<CH, CHK>;
         constexpr int FEAT_OFS = (int)(offsetof(Chunk, feat) / sizeof(float));
         b_stride = n < 16 ? CH : (int)(sizeof(FwdEntry) / sizeof(float));
         b_off = n < 16 ? FEAT_OFS + n : (int)(offsetof(FwdEntry, cd) / sizeof(float)) + ((n - 16) & 3);
+        b_adj = n < 16 ? (int)(sizeof(FwdEntry) / sizeof(float)) : 0;
     }
 
-    // software pipeline: the splat records of chunk k+1 and the list ids of chunk k+2 are requested while chunk k
+    // software pipeline: the splat records of round k+1 and the list ids of round k+2 are requested while round k
     // is blended, so neither of the two dependent gathers (id, then record) is ever waited for on the spot
     uint32_t n_id = 0, f_id = 0;
     float4 n_q0 = make_float4(0, 0, 0, 0), n_q1 = n_q0;
     float2 n_q2 = make_float2(0, 0);          // blue, depth (the radius half of q2 is not needed here)
-    if (lane < CHK && r_lo + lane < r_hi) n_id = a.point_list[r_lo + lane];
-    if (lane < CHK && r_lo + CHK + lane < r_hi) f_id = a.point_list[r_lo + CHK + lane];
-    if (lane < CHK && r_lo + lane < r_hi) {
+    if (lane < RND && r_lo + lane < r_hi) n_id = a.point_list[r_lo + lane];
+    if (lane < RND && r_lo + RND + lane < r_hi) f_id = a.point_list[r_lo + RND + lane];
+    if (lane < RND && r_lo + lane < r_hi) {
         const SplatRec* rp = a.rec + n_id;
         n_q0 = rp->q0; n_q1 = rp->q1; n_q2 = *reinterpret_cast<const float2*>(&rp->q2);
     }
 
-    for (uint32_t base = r_lo; base < r_hi; base += CHK) {
-        if constexpr (BASE) {
-            bool anylive = false;
+    // (BASE) any pixel of the quadrant still blending?
+    auto quad_live = [&]() __attribute__((always_inline)) {
+        bool anylive = false;
 #pragma unroll
-            for (int p = 0; p < PPL; p++) anylive = anylive || T[p] > 0.0f;
-            if (!__any(anylive)) break;
-        }
-        const int cnt_in = (int)min((uint32_t)CHK, r_hi - base);
+        for (int p = 0; p < PPL; p++) anylive = anylive || T[p] > 0.0f;
+        return __any(anylive) != 0;
+    };
+
+    // One round: the RND list positions from `base` on against the wave's pixel block; the hits, compacted in list order, go to
+    // ent[tail ..) (modulo QN); then the prefetch moves on one round.  Returns the number of hits.
+    auto test_round = [&](const uint32_t base, const int tail) __attribute__((always_inline)) {
+        const int cnt_in = (int)min((uint32_t)RND, r_hi - base);
         // wave-level culling: drop splats whose 1/255 footprint misses this wave's pixel block, compact the rest
         const bool hit = lane < cnt_in && rect_hit(n_q0.x, n_q0.y, n_q0.z, n_q0.w, n_q1.x, n_q1.y, (float)sgpr_opaque(iwx0),
                                                    (float)sgpr_opaque(iwx1), (float)sgpr_opaque(iwy0), (float)sgpr_opaque(iwy1));
         const unsigned long long hmask = __ballot(hit);
         const int cnt = __popcll(hmask);
-        const int slot = __popcll(hmask & ((1ull << lane) - 1ull));
+        int slot = tail + __popcll(hmask & ((1ull << lane) - 1ull));
+        if constexpr (QN > CHK) slot = slot >= QN ? slot - QN : slot;
         __builtin_amdgcn_wave_barrier();
         if (hit) {
             FwdEntry en;
@@ -416,14 +443,20 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
             ck.ent[slot] = en;
         }
         __builtin_amdgcn_wave_barrier();
-        // prefetch: records of the next chunk (its ids arrived during the previous chunk), ids of the one after
+        // prefetch: records of the next round (its ids arrived during the previous round), ids of the one after
         n_id = f_id;
-        if (lane < CHK && base + CHK + lane < r_hi) {
+        if (lane < RND && base + RND + lane < r_hi) {
             const SplatRec* rp = a.rec + n_id;
             n_q0 = rp->q0; n_q1 = rp->q1; n_q2 = *reinterpret_cast<const float2*>(&rp->q2);
         }
-        if (lane < CHK && base + 2 * CHK + lane < r_hi) f_id = a.point_list[base + 2 * CHK + lane];
+        if (lane < RND && base + 2 * RND + lane < r_hi) f_id = a.point_list[base + 2 * RND + lane];
+        return cnt;
+    };
 
+    // One chunk: the cnt <= CHK entries ent[head ..) (head + cnt <= QN: a chunk does not wrap) - their feature rows are fetched
+    // into the chunk image, then they are blended in order.
+    auto blend_chunk = [&](const int head, const int cnt) __attribute__((always_inline)) {
+        FwdEntry* const ent = ck.ent + head;
         // feature rows of the chunk -> LDS (coalesced: CH/4 lanes x 16 B per instance).  Full-width windows go through
         // LDS-direct loads (global_load_lds_dwordx4: lane l of a request lands at base + 16 l, which IS the row-major
         // image because element e = 64 it + lane sits at byte 16 e): all requests of the chunk are in flight together
@@ -438,7 +471,7 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
             for (int it = 0; it < CHK * CHV / 64; it++) {
                 const int e = it * 64 + lane;
                 if (e < cnt * CHV) {
-                    const uint32_t g = ck.ent[e / CHV].id;
+                    const uint32_t g = ent[e / CHV].id;
                     const float* src = a.feat + (size_t)g * a.C + a.c0 + 4 * (e % CHV);
                     __builtin_amdgcn_global_load_lds((gbl_ptr)src, (lds_ptr)&ck.feat[it * 256], 16, 0, 0);
                 }
@@ -448,7 +481,7 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
         } else {
             for (int e = lane; e < cnt * CHV; e += 64) {
                 const int inst = e / CHV, v = e % CHV;
-                const uint32_t g = ck.ent[inst].id;
+                const uint32_t g = ent[inst].id;
                 const float* src = a.feat + (size_t)g * a.C + a.c0 + 4 * v;
                 float4 f;
                 if (vec_ok && 4 * v + 3 < a.nc) {
@@ -463,17 +496,48 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
             }
         }
         // an odd (not a multiple of GI) count is padded with null entries - opacity 0: alpha = 0 fails the 1/255 test at every
-        // pixel; a zero feature row - so that the blend loop below needs no "is there a second entry" logic at all
+        // pixel; a zero feature row - so that the blend loop below needs no "is there a second entry" logic at all.  (With the
+        // ring only the last chunk of a list can be short; the slot behind it is free: head + cnt < head + CHK.)
         if ((cnt & (GI - 1)) != 0) {
             for (int q = cnt; q < ((cnt + GI - 1) & ~(GI - 1)); q++) {
-                if (lane < 12) reinterpret_cast<float*>(&ck.ent[q])[lane] = 0.0f;
+                if (lane < 12) reinterpret_cast<float*>(&ent[q])[lane] = 0.0f;
                 for (int c = lane; c < CH; c += 64) ck.feat[q * CH + c] = 0.0f;
             }
         }
         __builtin_amdgcn_wave_barrier();
 
+        // (CH = 16) the B columns are addressed from the chunk's first entry: the feature rows lie `head` entries nearer
+        const int b_off_c = (CH == 16 && QN > CHK) ? b_off - head * b_adj : b_off;
         for (int j = 0; j < cnt; j += GI)
-            fwd_blend_group<CH, PPL, GI, BASE>(ck.ent, ck.feat, reinterpret_cast<const float*>(&ck), j, lane, b_stride, b_off, FW_DEV_SKIP(256), px);
+            fwd_blend_group<CH, PPL, GI, BASE>(ent, ck.feat, reinterpret_cast<const float*>(ent), j, lane, b_stride, b_off_c, FW_DEV_SKIP(256), px);
+    };
+
+    if constexpr (RND == CHK) {
+        for (uint32_t base = r_lo; base < r_hi; base += CHK) {
+            if (BASE && !quad_live()) break;
+            const int cnt = test_round(base, 0);
+            blend_chunk(0, cnt);
+        }
+    } else {
+        // qh: first queued entry (0, CHK or 2 CHK), qn: entries queued.  The saturation test runs before every round and before
+        // every chunk; what is still queued when the quadrant saturates is dropped (a finished pixel ignores every entry).
+        // (ONE blend_chunk site in a plain loop nest, the drain folded into the chunk loop of the last round: with a second site
+        // behind the loop, or with rounds and chunks as the two arms of one loop, the register allocator keeps the 32 accumulators
+        // in two places and copies them per chunk - 16 to 32 v_mov_b64 per iteration, 128 registers instead of 100.)
+        int qh = 0, qn = 0;
+        for (uint32_t base = r_lo; base < r_hi; base += RND) {
+            if (BASE && !quad_live()) break;
+            qn += test_round(base, qh + qn);      // qh + qn <= 2 CHK + CHK - 1: the tail itself does not wrap, a hit's slot may
+            // whole chunks - and behind the last round the rest of the queue, padded to the group size
+            const int keep = base + RND < r_hi ? CHK - 1 : 0;
+            while (qn > keep) {
+                if (BASE && !quad_live()) { qn = 0; break; }
+                const int cnt = min(qn, CHK);
+                blend_chunk(qh, cnt);
+                qh = qh + CHK >= QN ? 0 : qh + CHK;
+                qn -= cnt;
+            }
+        }
     }
 
     const size_t HW = (size_t)a.W * a.H;
@@ -499,7 +563,8 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
         // D[i][n]: lane holds column n = lane & 31 (channel), register r holds row i = (r&3) + 8(r>>2) + 4(lane>>5)
         // (pixel 32h + i of this slot).  Transpose through LDS so that lanes are pixels again: [channel][65] in one go, or
         // (TS = 33) one half of the pixels at a time - the lanes of half h then write their own pixels.
-        constexpr int TS = FwdChunkMF<CH, CHK>::TS;
+        constexpr int TS = Chunk::TS;
+        float* const tile = ck.tile();
         constexpr int NH = TS == 33 ? 2 : 1;          // transpose rounds per column block
 #pragma unroll
         for (int nb = 0; nb < NB; nb++) {
@@ -511,7 +576,7 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
                         const int i = (NH == 2 ? 0 : 32 * h) + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                        ck.feat[(lane & 31) * TS + i] = acc[p][h][nb][r];
+                        tile[(lane & 31) * TS + i] = acc[p][h][nb][r];
                     }
                 __builtin_amdgcn_wave_barrier();
                 const int col = NH == 2 ? (lane & 31) : lane;
@@ -519,17 +584,17 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
 #pragma unroll 8
                     for (int n = 0; n < (CH < 32 ? CH : 32); n++)
                         if (32 * nb + n < a.nc)
-                            a.out_feat[(size_t)(a.c0 + 32 * nb + n) * HW + (size_t)pix_id[p]] = ck.feat[n * TS + col];
+                            a.out_feat[(size_t)(a.c0 + 32 * nb + n) * HW + (size_t)pix_id[p]] = tile[n * TS + col];
                     if constexpr (CDB) {
                         if (a.write_base) {      // columns 16..19 of the contraction: red, green, blue, depth
                             const size_t pid = (size_t)pix_id[p];
                             const float Tf = fabsf(T[p]);
                             a.final_T[pid] = Tf;
                             a.n_contrib[pid] = last[p];
-                            a.out_color[pid] = ck.feat[16 * TS + col] + Tf * a.bg[0];
-                            a.out_color[HW + pid] = ck.feat[17 * TS + col] + Tf * a.bg[1];
-                            a.out_color[2 * HW + pid] = ck.feat[18 * TS + col] + Tf * a.bg[2];
-                            a.out_depth[pid] = ck.feat[19 * TS + col];
+                            a.out_color[pid] = tile[16 * TS + col] + Tf * a.bg[0];
+                            a.out_color[HW + pid] = tile[17 * TS + col] + Tf * a.bg[1];
+                            a.out_color[2 * HW + pid] = tile[18 * TS + col] + Tf * a.bg[2];
+                            a.out_depth[pid] = tile[19 * TS + col];
                         }
                     }
                 }
@@ -543,17 +608,24 @@ __device__ __forceinline__ void render_forward_mfma_body(const FwdArgs& a) {
 // at three waves, 0.42-0.43 for two quadrants per wave with 64-instance chunks at three waves: 168 registers, 11.4 KB).
 // 64 channels, same shape: 150 registers and 9.7 KB, three waves per SIMD (c4: 2.58 -> 2.23 ms with 64-instance chunks at
 // two).  128 channels: 128 accumulator registers per quadrant, two waves per SIMD.
+// The w4 shapes (16 and 32 channels) test 64 list positions per round and blend from the ring (8.5 and 8.1 KB per wave: sixteen
+// waves per CU stay within the 160 KB); _w4_r32 keeps the 32-candidate rounds (option fwd_round = 32).  The 64- and 128-channel
+// shapes keep the 32-candidate rounds.
 template <int CH, bool BASE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) render_forward_mfma_kernel_w4(FwdArgs a) {
-    render_forward_mfma_body<CH, 1, 32, 2, BASE>(a);
+    render_forward_mfma_body<CH, 1, 32, 2, BASE, 64>(a);
+}
+template <int CH, bool BASE>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) render_forward_mfma_kernel_w4_r32(FwdArgs a) {
+    render_forward_mfma_body<CH, 1, 32, 2, BASE, 32>(a);
 }
 template <int CH, bool BASE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) render_forward_mfma_kernel_w3(FwdArgs a) {
-    render_forward_mfma_body<CH, 1, 32, 2, BASE>(a);
+    render_forward_mfma_body<CH, 1, 32, 2, BASE, 32>(a);
 }
 template <int CH, bool BASE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) render_forward_mfma_kernel_w2(FwdArgs a) {
-    render_forward_mfma_body<CH, 1, 32, 2, BASE>(a);
+    render_forward_mfma_body<CH, 1, 32, 2, BASE, 32>(a);
 }
 
 // The 128-channel shape needs 70 KB of LDS per four-wave workgroup (above the 64 KB default limit): the limit is raised once
@@ -566,7 +638,7 @@ bool wide_shape_usable() {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return false;
     if (state[dev].load(std::memory_order_acquire) == 0) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_forward_mfma_kernel_w2<128, BASE>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * sizeof(FwdChunkMF<128, 32>)));
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * sizeof(FwdChunkMF<128, 32, 32>)));
         if (e != hipSuccess) (void)hipGetLastError();     // not sticky: the narrower windows take over
         state[dev].store(e == hipSuccess ? 1 : -1, std::memory_order_release);
     }
@@ -576,10 +648,13 @@ bool wide_shape_usable() {
 template <int CH, bool BASE>
 void launch_shape(const FwdArgs& a, hipStream_t s) {
     const bool solo = a.solo != 0;
-    const size_t lds = (solo ? 1 : 4) * sizeof(FwdChunkMF<CH, 32>);
+    const bool ring = CH <= 32 && options().fwd_round != 32;
+    const size_t lds = (solo ? 1 : 4) * (ring ? sizeof(FwdChunkMF<CH, 32, 96>) : sizeof(FwdChunkMF<CH, 32, 32>));
     const dim3 grid(solo ? 4 * a.gx * a.gy : a.gx * a.gy), block(solo ? 64 : 256);
-    if constexpr (CH <= 32) hipLaunchKernelGGL((render_forward_mfma_kernel_w4<CH, BASE>), grid, block, lds, s, a);
-    else if constexpr (CH <= 64) hipLaunchKernelGGL((render_forward_mfma_kernel_w3<CH, BASE>), grid, block, lds, s, a);
+    if constexpr (CH <= 32) {
+        if (ring) hipLaunchKernelGGL((render_forward_mfma_kernel_w4<CH, BASE>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((render_forward_mfma_kernel_w4_r32<CH, BASE>), grid, block, lds, s, a);
+    } else if constexpr (CH <= 64) hipLaunchKernelGGL((render_forward_mfma_kernel_w3<CH, BASE>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((render_forward_mfma_kernel_w2<CH, BASE>), grid, block, lds, s, a);
 }
 template <int CH>

@@ -19,6 +19,7 @@ any of them, the counts are the last call's).
 """
 from __future__ import annotations
 
+import gc
 from typing import Callable, Optional
 
 import torch
@@ -58,8 +59,20 @@ class CapturedStep:
                     self.fn()
             self.stream.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self.stream):
-                self.result = self.fn()
+            # No cyclic garbage collection inside the capture.  `torch.cuda.graph` no longer collects on entry, so a dead
+            # reference cycle that holds an earlier graph (a dropped CapturedTrainer is one: trainer -> entry -> step -> fn ->
+            # trainer) survives until the collector happens to run - and if that is in the middle of this capture, the old graph's
+            # destructor releases its memory pool with calls that are not allowed while a stream is capturing: the process aborts.
+            # Collect now, outside the capture, and keep the collector off until the capture has ended.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g, stream=self.stream):
+                    self.result = self.fn()
+            finally:
+                if gc_was_on:
+                    gc.enable()
             self.counts_address = self._C.forward_counts_address()
             torch.cuda.current_stream().wait_stream(self.stream)
         finally:

@@ -125,6 +125,8 @@ const char* f3dgs_last_error(void);
  *                    the column blocks are split over the four waves by quadrants as well (no wave without matrix work, partial
  *                    sums added in the flush), 0 by columns only
  *   "fwd_wide"       blend forward: 1 (default) 128-channel windows where more than 64 channels remain
+ *   "fwd_round"      blend forward, matrix shapes of 5..32 channels: list positions a wave tests per round.  64 (default): the hits
+ *                    are queued and blended in full chunks of 32; 32: one chunk per round.  Same results bit for bit
  *   "fwd_solo"       blend forward: 1 (default) one 64-thread workgroup per quadrant wave
  *   "sync_free"      0: f3dgs_forward waits for the instance count where the reference does
  *                    (rasterizer_impl.cu:283; here behind the enqueue of the depth sort) and carves the binning buffer for
@@ -1379,6 +1381,7 @@ void f3dgs_set_grad_rows_ready_callback(f3dgs_rows_fn fn, void* ctx, int chunks)
  *         "counters"(16 x u32: [0] = entries of point_list,
  *         [1] = reference-style num_rendered)  "point_list"(u32 x R)  "tile_sorted"(u32 x R)
  *         "ranges"(uint2 per tile)  "final_T"(float per pixel)  "n_contrib"(u32 per pixel)
+ *         "tile_len"(u32 per tile: the largest n_contrib of its pixels)
  */
 int f3dgs_debug_read(
     const char* what,
