@@ -405,7 +405,7 @@ CountReadback* count_readback(hipStream_t s, bool may_create) {
 
 extern "C" {
 
-int f3dgs_version(void) { return 32500; }   // 3.23.0 (major * 10000 + minor * 100 + patch): 3.23 f3dgs_activate_forward, f3dgs_activate_backward, f3dgs_densify_stats; 3.22 f3dgs_codebook_assign, f3dgs_codebook_update; 3.21 f3dgs_transform_gaussians; 3.20 f3dgs_group_stats, f3dgs_group_merge; 3.19 f3dgs_knn_components, f3dgs_component_filter; 3.18 f3dgs_knn_neighbors, f3dgs_label_mode_filter, option knn_outward; 3.17 f3dgs_instance_associate, f3dgs_instance_merge; 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
+int f3dgs_version(void) { return 32600; }   // 3.26.0 (major * 10000 + minor * 100 + patch): 3.26 f3dgs_sam_decoder_*; 3.23 f3dgs_activate_forward, f3dgs_activate_backward, f3dgs_densify_stats; 3.22 f3dgs_codebook_assign, f3dgs_codebook_update; 3.21 f3dgs_transform_gaussians; 3.20 f3dgs_group_stats, f3dgs_group_merge; 3.19 f3dgs_knn_components, f3dgs_component_filter; 3.18 f3dgs_knn_neighbors, f3dgs_label_mode_filter, option knn_outward; 3.17 f3dgs_instance_associate, f3dgs_instance_merge; 3.16 f3dgs_label_votes, f3dgs_mask_instance_map; 3.15 f3dgs_mask_regions; 3.14 f3dgs_sam_masks, f3dgs_sam_upscale, f3dgs_box_nms, f3dgs_mask_rle_count / _emit, f3dgs_mask_unpack; 3.13 f3dgs_seg_metrics, f3dgs_seg_colorize; 3.12 f3dgs_contributions; 3.11 f3dgs_image_metrics; 3.10 f3dgs_view_*; 3.9 f3dgs_feature_pca_*; 3.8 f3dgs_segment; 3.7 f3dgs_edit_select; 3.6 f3dgs_image_loss_*; 3.5 options sync_free / instance_capacity, graph capture, f3dgs_forward_counts; 3.1 seven untested shape knobs removed, f3dgs_option_name; 3.2 f3dgs_set_feature_grad_lowres; 3.3 option bwd_bf16, 16-byte alignment checked; 3.4 bwd_bf16 = -1 (by the frame's conditioning), f3dgs_last_backward_contraction
 
 int f3dgs_last_backward_contraction(void) { return g_last_bwd_bf16.load(); }
 

@@ -613,6 +613,70 @@ torch::Tensor SamUpscale(const torch::Tensor& low_res, int64_t S, int64_t ih, in
     return out;
 }
 
+// SAM's prompt encoder and mask decoder (include/f3dgs.h: f3dgs_sam_decoder_*; sam_decoder.py checks names, shapes and the
+// architecture and raises KeyError / ValueError / NotImplementedError - the checks here guard the pointers).
+// params: F3DGS_SAM_DECODER_PARAMS contiguous float32 tensors on one HIP device, in the header's order -> the packed weights
+torch::Tensor SamDecoderPack(const std::vector<torch::Tensor>& params) {
+    TORCH_CHECK((int)params.size() == F3DGS_SAM_DECODER_PARAMS, "sam_decoder_pack: ", F3DGS_SAM_DECODER_PARAMS, " parameters expected, got ", params.size());
+    std::vector<const float*> table;
+    for (const torch::Tensor& p : params) {
+        TORCH_CHECK(p.is_cuda() && p.device() == params[0].device() && p.scalar_type() == torch::kFloat32 && p.is_contiguous(),
+                    "sam_decoder_pack: contiguous float32 parameters on one HIP device expected (no CPU path)");
+        table.push_back(p.data_ptr<float>());
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(params[0].device());
+    torch::Tensor packed = torch::empty({(long long)(f3dgs_sam_decoder_weights_bytes() / sizeof(float))}, params[0].options());
+    check_status(f3dgs_sam_decoder_pack_weights(table.data(), (int)table.size(), packed.data_ptr<float>(), current_stream(packed)), "sam_decoder_pack");
+    return packed;
+}
+
+// features (256,h,w) float32 with any non-negative strides (read in place) -> the image plan
+torch::Tensor SamDecoderPlan(const torch::Tensor& packed, const torch::Tensor& features) {
+    TORCH_CHECK(features.is_cuda() && features.scalar_type() == torch::kFloat32 && features.dim() == 3,
+                "sam_decoder_plan: features must be float32 (256,h,w) on a HIP device (no CPU path)");
+    TORCH_CHECK(packed.is_cuda() && packed.device() == features.device() && packed.scalar_type() == torch::kFloat32 && packed.is_contiguous() &&
+                    packed.numel() * sizeof(float) == f3dgs_sam_decoder_weights_bytes(), "sam_decoder_plan: packed weights on the features' device expected");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(features.device());
+    const int h = (int)features.size(1), w = (int)features.size(2);
+    const size_t bytes = f3dgs_sam_decoder_plan_bytes(h, w);
+    torch::Tensor plan = torch::empty({(long long)(bytes / sizeof(float))}, packed.options());
+    check_status(f3dgs_sam_decoder_plan((int)features.size(0), h, w, features.data_ptr<float>(), features.stride(0), features.stride(1), features.stride(2),
+                                        packed.data_ptr<float>(), bytes ? plan.data_ptr<float>() : nullptr, current_stream(features)),
+                 "sam_decoder_plan");
+    return plan;
+}
+
+// coords (B,n,2) float32, labels (B,n) int32, boxes (B,4) float32 or None -> (low_res (B,m,4h,4w), iou (B,m)), m = 3 or 1
+std::tuple<torch::Tensor, torch::Tensor> SamDecoderPredict(const torch::Tensor& plan, const torch::Tensor& packed, int64_t h, int64_t w,
+                                                           const torch::Tensor& coords, const torch::Tensor& labels,
+                                                           const c10::optional<torch::Tensor>& boxes, int64_t input_h, int64_t input_w, bool multimask) {
+    TORCH_CHECK(plan.is_cuda() && packed.is_cuda() && plan.device() == packed.device() && plan.is_contiguous() && packed.is_contiguous(),
+                "sam_decoder_predict: plan and packed weights on one HIP device expected");
+    TORCH_CHECK(h >= 1 && w >= 1 && h * w <= F3DGS_SAM_DECODER_MAX_GRID && plan.numel() * sizeof(float) == f3dgs_sam_decoder_plan_bytes((int)h, (int)w) &&
+                    packed.numel() * sizeof(float) == f3dgs_sam_decoder_weights_bytes(), "sam_decoder_predict: the plan is not one of an ", h, " x ", w, " grid");
+    TORCH_CHECK(coords.device() == plan.device() && coords.scalar_type() == torch::kFloat32 && coords.dim() == 3 && coords.size(2) == 2 &&
+                    coords.is_contiguous(), "sam_decoder_predict: coords must be contiguous float32 (B,n,2) on the plan's device");
+    const int64_t B = coords.size(0), n = coords.size(1);
+    TORCH_CHECK(labels.device() == plan.device() && labels.scalar_type() == torch::kInt32 && labels.dim() == 2 && labels.size(0) == B &&
+                    labels.size(1) == n && labels.is_contiguous(), "sam_decoder_predict: labels must be contiguous int32 (B,n) on the plan's device");
+    if (boxes)
+        TORCH_CHECK(boxes->device() == plan.device() && boxes->scalar_type() == torch::kFloat32 && boxes->dim() == 2 && boxes->size(0) == B &&
+                        boxes->size(1) == 4 && boxes->is_contiguous(), "sam_decoder_predict: boxes must be contiguous float32 (B,4) on the plan's device");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(plan.device());
+    const int64_t m = multimask ? 3 : 1;
+    torch::Tensor low_res = torch::empty({B, m, 4 * h, 4 * w}, plan.options()), iou = torch::empty({B, m}, plan.options());
+    if (B == 0) return {low_res, iou};
+    const int T = (int)(5 + n + (boxes ? 2 : 1));
+    const size_t bytes = f3dgs_sam_decoder_scratch_bytes((int)B, (int)h, (int)w, T);
+    torch::Tensor scratch = torch::empty({(long long)std::max<size_t>(bytes, 16)}, plan.options().dtype(torch::kByte));
+    const int rc = f3dgs_sam_decoder_predict((int)B, (int)h, (int)w, (int)n, n ? coords.data_ptr<float>() : nullptr, n ? labels.data_ptr<int32_t>() : nullptr,
+                                             boxes ? boxes->data_ptr<float>() : nullptr, (int)input_h, (int)input_w, multimask ? 1 : 0,
+                                             plan.data_ptr<float>(), packed.data_ptr<float>(), low_res.data_ptr<float>(), iou.data_ptr<float>(),
+                                             scratch.data_ptr(), bytes, current_stream(plan));
+    check_status(rc, "sam_decoder_predict");
+    return {low_res, iou};
+}
+
 // boxes (M,4) float32 IN SCORE ORDER, categories (M) int32 or None, order (M) int32 or None.  Returns (keep (M) int32, count (1) int32).
 std::tuple<torch::Tensor, torch::Tensor> BoxNms(const torch::Tensor& boxes, const c10::optional<torch::Tensor>& categories,
                                                 double iou_threshold, const c10::optional<torch::Tensor>& order) {
@@ -1479,6 +1543,10 @@ PYBIND11_MODULE(_C, m) {
           py::arg("t_lo"), py::arg("stability_thresh"), py::arg("edge_filter"));
     m.def("sam_upscale", &SamUpscale, py::arg("low_res"), py::arg("S"), py::arg("ih"), py::arg("iw"), py::arg("H"), py::arg("W"), py::arg("t"),
           py::arg("out_bool"));
+    m.def("sam_decoder_pack", &SamDecoderPack, py::arg("params"));
+    m.def("sam_decoder_plan", &SamDecoderPlan, py::arg("packed"), py::arg("features"));
+    m.def("sam_decoder_predict", &SamDecoderPredict, py::arg("plan"), py::arg("packed"), py::arg("h"), py::arg("w"), py::arg("coords"),
+          py::arg("labels"), py::arg("boxes"), py::arg("input_h"), py::arg("input_w"), py::arg("multimask"));
     m.def("box_nms", &BoxNms, py::arg("boxes"), py::arg("categories"), py::arg("iou_threshold"), py::arg("order"));
     m.def("mask_rle_count", &MaskRleCount, py::arg("packed"), py::arg("index"), py::arg("FH"));
     m.def("mask_rle_emit", &MaskRleEmit, py::arg("packed"), py::arg("index"), py::arg("FH"), py::arg("lens"), py::arg("ends"), py::arg("out"),

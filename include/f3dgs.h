@@ -1323,6 +1323,61 @@ int f3dgs_codebook_update(int P, int K, int C, const float* features, int64_t fe
                           int32_t* count /* K, or NULL */, void* scratch, size_t scratch_bytes, void* stream /* hipStream_t */);
 
 /*
+ * ---- SAM's prompt encoder and mask decoder (csrc/sam_decoder.hip; forward only) ---------------------------------------
+ * From a rendered 256-channel feature map and point / box prompts to the decoder's low-resolution logits and IoU
+ * predictions: what the reference's predictor.py:predict_torch gets from `prompt_encoder` and `mask_decoder` before
+ * `postprocess_masks`, and what f3dgs_sam_masks takes.  Exactly SAM's decoder: transformer_dim 256, depth 2, 8 heads, MLP 2048,
+ * attention downsample rate 2, 4 mask tokens + 1 IoU token, the 4x upscaler and the hypernetwork heads; any other architecture,
+ * and the mask prompt (`mask_downscaling`), are not built.  fp32 in, fp32 out; every contraction over a weight matrix on the
+ * exact-fp32 matrix instructions; no atomics, every reduction in a fixed order: two calls give the same bits, and a prompt's
+ * outputs are the same bits at every batch size and every position in the batch.
+ *
+ * f3dgs_sam_decoder_pack_weights: `params` is a HOST table of F3DGS_SAM_DECODER_PARAMS device pointers, each a contiguous fp32
+ * parameter of the reference's modules in this order (Linear weights (out, in), ConvTranspose2d weights (in, out, 2, 2)):
+ *   prompt_encoder:  pe_layer.positional_encoding_gaussian_matrix (2, 128); point_embeddings.0 .. 3.weight; not_a_point_embed.weight;
+ *                    no_mask_embed.weight
+ *   mask_decoder:    iou_token.weight; mask_tokens.weight (4, 256);
+ *                    for layer l = 0, 1 of transformer.layers: self_attn, norm1, cross_attn_token_to_image, norm2, mlp.lin1, mlp.lin2,
+ *                    norm3, norm4, cross_attn_image_to_token;
+ *                    transformer.final_attn_token_to_image; transformer.norm_final_attn;
+ *                    output_upscaling.0 (ConvTranspose2d), .1 (LayerNorm2d), .3 (ConvTranspose2d);
+ *                    output_hypernetworks_mlps.0 .. 3, each layers.0 .. 2; iou_prediction_head.layers.0 .. 2
+ *   where an attention is q_proj, k_proj, v_proj, out_proj and every module is its weight, then its bias.
+ * `packed`: f3dgs_sam_decoder_weights_bytes() bytes, 16-byte aligned, in the kernels' own layout.  One small launch per parameter.
+ *
+ * f3dgs_sam_decoder_plan (once per feature map): `features` C x h x w, read in place at the given element strides (a view of a
+ * larger render works).  Writes into `plan` (f3dgs_sam_decoder_plan_bytes(h, w) bytes, 16-byte aligned) what is the same for
+ * every prompt of the image: the token-major embedding + no_mask_embed, the dense positional encoding (cell centres
+ * (i + 0.5) / h, (j + 0.5) / w) and layer 0's projections of the image tokens.  Four launches.
+ *
+ * f3dgs_sam_decoder_predict: B prompts of n_points points each (`coords` B x n_points x 2 fp32 (x, y) in pixels of the
+ * input_h x input_w input image; `labels` B x n_points int32: 1 foreground, 0 background, -1 not a point) and, if `boxes` is not
+ * NULL, one box each (B x 4 fp32 XYXY).  The tokens of a prompt are [iou, mask 0..3, points..., a pad point if no box is given,
+ * box corner 0, box corner 1]: T = 5 + n_points + (boxes ? 2 : 1) <= F3DGS_SAM_DECODER_MAX_TOKENS.  `low_res`: B x n x 4h x 4w
+ * fp32 and `iou`: B x n fp32 with n = 3 (masks 1..3) if multimask, else 1 (mask 0); only these are computed.  `scratch`:
+ * f3dgs_sam_decoder_scratch_bytes(B, h, w, T) bytes, 16-byte aligned, uninitialised (it holds the prompts' image tokens: B h w
+ * KiB and a little).  B == 0 is a no-op.  40 launches, none of them a memset; no host read, no allocation, every launch on
+ * `stream`: capturable.
+ *
+ * F3DGS_ERR_INVALID_ARGUMENT before any device work: a size below its minimum, a NULL or misaligned pointer, a negative stride,
+ * no prompt at all, a scratch too small.  F3DGS_ERR_UNSUPPORTED: C != 256, h w > F3DGS_SAM_DECODER_MAX_GRID, T >
+ * F3DGS_SAM_DECODER_MAX_TOKENS, B > 65535.  The _bytes functions return 0 for sizes the calls refuse.
+ */
+#define F3DGS_SAM_DECODER_PARAMS 127
+#define F3DGS_SAM_DECODER_MAX_TOKENS 16
+#define F3DGS_SAM_DECODER_MAX_GRID 16384
+size_t f3dgs_sam_decoder_weights_bytes(void);
+int f3dgs_sam_decoder_pack_weights(const float* const* params /* host table of device pointers */, int n_params, float* packed,
+                                   void* stream /* hipStream_t */);
+size_t f3dgs_sam_decoder_plan_bytes(int h, int w);
+int f3dgs_sam_decoder_plan(int C, int h, int w, const float* features, int64_t stride_c, int64_t stride_y, int64_t stride_x /* in elements */,
+                           const float* packed, float* plan, void* stream /* hipStream_t */);
+size_t f3dgs_sam_decoder_scratch_bytes(int B, int h, int w, int T);
+int f3dgs_sam_decoder_predict(int B, int h, int w, int n_points, const float* coords, const int32_t* labels, const float* boxes /* or NULL */,
+                              int input_h, int input_w, int multimask, const float* plan, const float* packed, float* low_res, float* iou,
+                              void* scratch, size_t scratch_bytes, void* stream /* hipStream_t */);
+
+/*
  * ---- Side channels of f3dgs_backward: threading contract -----------------------------------------------------------
  * The four setters below and f3dgs_set_feature_grad_lowres change how the f3dgs_backward calls OF THE CALLING HOST THREAD
  * behave.  All five are thread-local: they are invisible to, and unaffected by, any other thread.
