@@ -677,6 +677,77 @@ std::tuple<torch::Tensor, torch::Tensor> SamDecoderPredict(const torch::Tensor& 
     return {low_res, iou};
 }
 
+// LPIPS, VGG16 (include/f3dgs.h: f3dgs_lpips_*; lpips_vgg.py checks names, shapes and arguments and raises KeyError / ValueError /
+// NotImplementedError - the checks here guard the pointers).
+// params: F3DGS_LPIPS_PARAMS contiguous float32 tensors on one HIP device, in the header's order -> the packed weights
+torch::Tensor LpipsPack(const std::vector<torch::Tensor>& params) {
+    TORCH_CHECK((int)params.size() == F3DGS_LPIPS_PARAMS, "lpips_pack: ", F3DGS_LPIPS_PARAMS, " parameters expected, got ", params.size());
+    std::vector<const float*> table;
+    for (const torch::Tensor& p : params) {
+        TORCH_CHECK(p.is_cuda() && p.device() == params[0].device() && p.scalar_type() == torch::kFloat32 && p.is_contiguous(),
+                    "lpips_pack: contiguous float32 parameters on one HIP device expected (no CPU path)");
+        table.push_back(p.data_ptr<float>());
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(params[0].device());
+    torch::Tensor packed = torch::empty({(long long)(f3dgs_lpips_weights_bytes() / sizeof(float))}, params[0].options());
+    check_status(f3dgs_lpips_pack_weights(table.data(), (int)table.size(), packed.data_ptr<float>(), current_stream(packed)), "lpips_pack");
+    return packed;
+}
+
+static void lpips_check_image(const torch::Tensor& t, const torch::Tensor& packed, const char* where, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.size(1) == 3 && (t.scalar_type() == torch::kFloat32 || t.scalar_type() == torch::kByte),
+                where, ": ", name, " must be float32 or uint8 (N,3,H,W) on a HIP device (no CPU path)");
+    TORCH_CHECK(packed.is_cuda() && packed.device() == t.device() && packed.scalar_type() == torch::kFloat32 && packed.is_contiguous() &&
+                    packed.numel() * sizeof(float) == f3dgs_lpips_weights_bytes(), where, ": packed weights on the images' device expected");
+    for (int d = 0; d < 4; d++) TORCH_CHECK(t.stride(d) >= 0, where, ": ", name, " has a negative stride");
+}
+
+int64_t LpipsWorkspaceBytes(int64_t N, int64_t H, int64_t W) { return (int64_t)f3dgs_lpips_workspace_bytes((int)N, (int)H, (int)W); }
+
+// x, y (N,3,H,W) float32 or uint8 with any non-negative strides (read in place) -> (layer_terms (N,5), totals (N))
+std::tuple<torch::Tensor, torch::Tensor> LpipsForward(const torch::Tensor& packed, const torch::Tensor& x, const torch::Tensor& y, int64_t flags) {
+    lpips_check_image(x, packed, "lpips_forward", "x");
+    lpips_check_image(y, packed, "lpips_forward", "y");
+    TORCH_CHECK(x.sizes() == y.sizes() && x.device() == y.device(), "lpips_forward: x ", x.sizes(), " and y ", y.sizes(), " must agree, on one device");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    const int64_t N = x.size(0), H = x.size(2), W = x.size(3);
+    torch::Tensor terms = torch::empty({N, 5}, packed.options()), totals = torch::empty({N}, packed.options());
+    if (N == 0) return {terms, totals};
+    const size_t bytes = f3dgs_lpips_workspace_bytes((int)N, (int)H, (int)W);
+    TORCH_CHECK(bytes > 0, "lpips_forward: ", N, " pairs of ", H, " x ", W, " are not taken (H, W >= 16)");
+    torch::Tensor ws = torch::empty({(long long)bytes}, packed.options().dtype(torch::kByte));
+    const int rc = f3dgs_lpips_forward((int)N, (int)H, (int)W, x.data_ptr(), x.scalar_type() == torch::kByte ? F3DGS_LPIPS_U8 : F3DGS_LPIPS_F32,
+                                       x.stride(0), x.stride(1), x.stride(2), x.stride(3), y.data_ptr(),
+                                       y.scalar_type() == torch::kByte ? F3DGS_LPIPS_U8 : F3DGS_LPIPS_F32, y.stride(0), y.stride(1), y.stride(2),
+                                       y.stride(3), (int)flags, packed.data_ptr<float>(), terms.data_ptr<float>(), totals.data_ptr<float>(),
+                                       ws.data_ptr(), bytes, current_stream(x));
+    check_status(rc, "lpips_forward");
+    return {terms, totals};
+}
+
+// image (N,3,H,W) -> the five un-normalised taps (N,C_l,H_l,W_l)
+std::vector<torch::Tensor> LpipsTaps(const torch::Tensor& packed, const torch::Tensor& image, bool quantize) {
+    lpips_check_image(image, packed, "lpips_taps", "image");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(image.device());
+    const int64_t N = image.size(0), H = image.size(2), W = image.size(3);
+    static const int64_t C[5] = {64, 128, 256, 512, 512};
+    std::vector<torch::Tensor> taps;
+    std::vector<float*> table;
+    for (int l = 0; l < 5; l++) {
+        taps.push_back(torch::empty({N, C[l], H >> l, W >> l}, packed.options()));
+        table.push_back(N ? taps[l].data_ptr<float>() : nullptr);
+    }
+    if (N == 0) return taps;
+    const size_t bytes = f3dgs_lpips_workspace_bytes((int)((N + 1) / 2), (int)H, (int)W);
+    TORCH_CHECK(bytes > 0, "lpips_taps: ", N, " images of ", H, " x ", W, " are not taken (H, W >= 16)");
+    torch::Tensor ws = torch::empty({(long long)bytes}, packed.options().dtype(torch::kByte));
+    const int rc = f3dgs_lpips_taps((int)N, (int)H, (int)W, image.data_ptr(), image.scalar_type() == torch::kByte ? F3DGS_LPIPS_U8 : F3DGS_LPIPS_F32,
+                                    image.stride(0), image.stride(1), image.stride(2), image.stride(3), quantize ? 1 : 0, packed.data_ptr<float>(),
+                                    table.data(), ws.data_ptr(), bytes, current_stream(image));
+    check_status(rc, "lpips_taps");
+    return taps;
+}
+
 // boxes (M,4) float32 IN SCORE ORDER, categories (M) int32 or None, order (M) int32 or None.  Returns (keep (M) int32, count (1) int32).
 std::tuple<torch::Tensor, torch::Tensor> BoxNms(const torch::Tensor& boxes, const c10::optional<torch::Tensor>& categories,
                                                 double iou_threshold, const c10::optional<torch::Tensor>& order) {
@@ -1547,6 +1618,12 @@ PYBIND11_MODULE(_C, m) {
     m.def("sam_decoder_plan", &SamDecoderPlan, py::arg("packed"), py::arg("features"));
     m.def("sam_decoder_predict", &SamDecoderPredict, py::arg("plan"), py::arg("packed"), py::arg("h"), py::arg("w"), py::arg("coords"),
           py::arg("labels"), py::arg("boxes"), py::arg("input_h"), py::arg("input_w"), py::arg("multimask"));
+    m.def("lpips_pack", &LpipsPack, py::arg("params"));
+    m.def("lpips_workspace_bytes", &LpipsWorkspaceBytes, py::arg("N"), py::arg("H"), py::arg("W"));
+    m.def("lpips_forward", &LpipsForward, py::arg("packed"), py::arg("x"), py::arg("y"), py::arg("flags"));
+    m.def("lpips_taps", &LpipsTaps, py::arg("packed"), py::arg("image"), py::arg("quantize"));
+    m.attr("LPIPS_QUANTIZE_X") = (int)F3DGS_LPIPS_QUANTIZE_X;
+    m.attr("LPIPS_QUANTIZE_Y") = (int)F3DGS_LPIPS_QUANTIZE_Y;
     m.def("box_nms", &BoxNms, py::arg("boxes"), py::arg("categories"), py::arg("iou_threshold"), py::arg("order"));
     m.def("mask_rle_count", &MaskRleCount, py::arg("packed"), py::arg("index"), py::arg("FH"));
     m.def("mask_rle_emit", &MaskRleEmit, py::arg("packed"), py::arg("index"), py::arg("FH"), py::arg("lens"), py::arg("ends"), py::arg("out"),

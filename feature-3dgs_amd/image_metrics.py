@@ -27,7 +27,8 @@ reference's reported numbers come out without the disk.  uint8 tensors - planar 
 over with `channels_last=True` - are read as they are, value v / 255.  The two sides choose their form independently:
 `quantize` and `channels_last` are one bool for both sides or an (image, gt) pair.
 
-LPIPS (metrics.py:74) is out of scope: it is a VGG network whose weights this repository does not hold.
+LPIPS (metrics.py:74) is lpips_vgg.py's: this repository holds no VGG weights, `evaluate_views(..., lpips_weights=...)` takes the
+caller's (lpips_vgg.LpipsWeights) and adds the third number.
 HIP only; no CPU fallback; argument errors are raised as ValueError before any device work.
 """
 from __future__ import annotations
@@ -125,13 +126,14 @@ def ssim(img1, img2, window_size=11, size_average=True):
     return per_image.mean() if size_average else per_image
 
 
-def evaluate_views(renders, gts, quantize=True, channels_last=False) -> dict:
+def evaluate_views(renders, gts, quantize=True, channels_last=False, lpips_weights=None) -> dict:
     """The image metrics of a test set as metrics.py:81-86 reports them: {"SSIM", "PSNR", "L1"} - the means over the views, formed
     as metrics.py forms them (`torch.tensor(values).mean().item()`) - and {"per_view": {"SSIM": [...], "PSNR": [...], "L1": [...]}}
     in the order of `renders`.  renders, gts: lists of (3,H,W) (any C) tensors of possibly different sizes; every run of
     equal-sized, equally typed views goes to the device in one call, and the host reads the results once, at the end.
     quantize (default True: the PNG round trip of metrics.py) applies to the float32 tensors only and channels_last to the
-    uint8 ones only."""
+    uint8 ones only.  lpips_weights (lpips_vgg.LpipsWeights): the result also carries "LPIPS" and per_view "LPIPS"
+    (lpips_vgg.evaluate_views, metrics.py:74; a second host read); None: exactly the three."""
     if len(renders) != len(gts):
         raise ValueError(f"{len(renders)} renders and {len(gts)} ground-truth images")
     cl = _pair(channels_last, "channels_last")
@@ -157,8 +159,18 @@ def evaluate_views(renders, gts, quantize=True, channels_last=False) -> dict:
             _prepare(renders[k], gts[k], qq, cc)
         runs.append((i, j, qq, cc))
         i = j
+    perceptual = None
+    if lpips_weights is not None:
+        import lpips_vgg
+
+        def planar(t, last):                                  # an interleaved uint8 view, read in place through its strides
+            return t.movedim(-1, -3) if last and torch.is_tensor(t) and t.dtype == torch.uint8 else t
+        perceptual = lpips_vgg.evaluate_views([planar(t, cl[0]) for t in renders], [planar(t, cl[1]) for t in gts], lpips_weights, q)
     if not runs:
-        return {"SSIM": float("nan"), "PSNR": float("nan"), "L1": float("nan"), "per_view": {"SSIM": [], "PSNR": [], "L1": []}}
+        empty = {"SSIM": float("nan"), "PSNR": float("nan"), "L1": float("nan"), "per_view": {"SSIM": [], "PSNR": [], "L1": []}}
+        if perceptual is not None:
+            empty["LPIPS"], empty["per_view"]["LPIPS"] = perceptual["LPIPS"], perceptual["per_view"]["LPIPS"]
+        return empty
     parts = []
     for i, j, qq, cc in runs:
         m = image_metrics(torch.stack([t if t.dim() == 3 else t[0] for t in renders[i:j]]),
@@ -170,6 +182,8 @@ def evaluate_views(renders, gts, quantize=True, channels_last=False) -> dict:
         values = table[row].tolist()
         out[name] = torch.tensor(values).mean().item()
         out["per_view"][name] = values
+    if perceptual is not None:
+        out["LPIPS"], out["per_view"]["LPIPS"] = perceptual["LPIPS"], perceptual["per_view"]["LPIPS"]
     return out
 
 

@@ -1378,6 +1378,57 @@ int f3dgs_sam_decoder_predict(int B, int h, int w, int n_points, const float* co
                               void* scratch, size_t scratch_bytes, void* stream /* hipStream_t */);
 
 /*
+ * ---- LPIPS, VGG16, version 0.1 (csrc/lpips.hip; forward only) -----------------------------------------------------------
+ * The third number of the reference's metrics.py:72-74, as its lpipsPyTorch computes it with net_type 'vgg': the z-score
+ * (mean -.030 -.088 -.188, std .458 .448 .450; values as given, no rescaling), torchvision's vgg16().features[0:30] (13
+ * convolutions 3x3 pad 1 with bias and ReLU, widths 64 64 | 128 128 | 256 x3 | 512 x3 | 512 x3, a 2x2 max-pool between the
+ * blocks), the taps behind relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 (C_l = 64, 128, 256, 512, 512 at H, H/2, H/4, H/8, H/16,
+ * floor), and per tap  d_l = mean over pixels of sum_c w_l[c] (x_c / (|x| + 1e-10) - y_c / (|y| + 1e-10))^2.  fp32 throughout,
+ * the contractions of conv1_2 .. conv5_3 on the exact-fp32 matrix instructions in ONE summation order (the accumulator starts
+ * at the bias; per chunk of 16 input channels the 144 products (tap; channel pair) are one chain from zero, and the chunk sums
+ * are added in chunk order), zeros outside the image: an activation is a function of its 3 x 3 x Cin inputs alone.  No atomics, every reduction in a fixed order: two calls give the same bits, and a pair's
+ * outputs are the same bits at every batch size and every position in the batch.  Other networks are not built.
+ *
+ * f3dgs_lpips_pack_weights: `params` is a HOST table of F3DGS_LPIPS_PARAMS device pointers, each a contiguous fp32 parameter:
+ * the 13 convolution weights (Cout, Cin, 3, 3) of features.0 2 5 7 10 12 14 17 19 21 24 26 28, then their 13 biases, then the
+ * five heads lin.0 .. 4 (C_l values each, non-negative in the published weights).  `packed`: f3dgs_lpips_weights_bytes() bytes,
+ * 16-byte aligned, in the kernels' own layout (59 MB).  One small launch per parameter.
+ *
+ * f3dgs_lpips_forward: N pairs of 3 x H x W images, H, W >= 16.  A side is read IN PLACE at the given element strides (all
+ * >= 0: a channels-last view, a crop of a larger tensor) in its format: F3DGS_LPIPS_F32 (4-byte aligned; with
+ * F3DGS_LPIPS_QUANTIZE_X / _Y in `flags` a value v is read as floor(clamp(v * 255 + 0.5, 0, 255)) / 255, what a saved PNG
+ * holds of it - f3dgs_image_metrics' rounding) or F3DGS_LPIPS_U8 (value / 255, bit for bit torch's quotient).  `layer_terms`
+ * (N x 5 fp32: d_l) and `totals` (N fp32: sum_l d_l) - either may be NULL.  `workspace`: f3dgs_lpips_workspace_bytes(N, H, W)
+ * bytes, 16-byte aligned, uninitialised: two activation buffers of 2N x 64 x H x W floats and the fp64 partial sums of the
+ * taps.  x and y run as one batch of 2N images: 13 convolution launches, 5 tap launches, 1 final sum.  No host read, no
+ * allocation, every launch on `stream`: capturable.  N == 0 is a no-op.
+ *
+ * f3dgs_lpips_taps: the five un-normalised taps of N images into `taps`, a HOST table of five device pointers (N x C_l x H_l
+ * x W_l fp32, contiguous).  `workspace`: f3dgs_lpips_workspace_bytes((N + 1) / 2, H, W) bytes.
+ *
+ * F3DGS_ERR_INVALID_ARGUMENT before any device work: N < 0, H or W < 16, a NULL or misaligned pointer, a negative stride, an
+ * unknown format or flag, a quantize flag on a uint8 side, a workspace too small.  F3DGS_ERR_UNSUPPORTED: more than 65534
+ * images or 2^26 pixels an image.  f3dgs_lpips_workspace_bytes returns 0 for sizes the calls refuse.
+ */
+#define F3DGS_LPIPS_PARAMS 31
+#define F3DGS_LPIPS_F32 0
+#define F3DGS_LPIPS_U8 1
+#define F3DGS_LPIPS_QUANTIZE_X 0x1
+#define F3DGS_LPIPS_QUANTIZE_Y 0x2
+size_t f3dgs_lpips_weights_bytes(void);
+int f3dgs_lpips_pack_weights(const float* const* params /* host table of device pointers */, int n_params, float* packed,
+                             void* stream /* hipStream_t */);
+size_t f3dgs_lpips_workspace_bytes(int N, int H, int W);
+int f3dgs_lpips_forward(int N, int H, int W, const void* x, int x_format, int64_t x_stride_n, int64_t x_stride_c, int64_t x_stride_y,
+                        int64_t x_stride_x /* in elements */, const void* y, int y_format, int64_t y_stride_n, int64_t y_stride_c,
+                        int64_t y_stride_y, int64_t y_stride_x, int flags, const float* packed, float* layer_terms /* N x 5, or NULL */,
+                        float* totals /* N, or NULL */, void* workspace, size_t workspace_bytes, void* stream /* hipStream_t */);
+int f3dgs_lpips_taps(int N, int H, int W, const void* image, int format, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                     int64_t stride_x /* in elements */, int quantize, const float* packed,
+                     float* const* taps /* host table of five device pointers */, void* workspace, size_t workspace_bytes,
+                     void* stream /* hipStream_t */);
+
+/*
  * ---- Side channels of f3dgs_backward: threading contract -----------------------------------------------------------
  * The four setters below and f3dgs_set_feature_grad_lowres change how the f3dgs_backward calls OF THE CALLING HOST THREAD
  * behave.  All five are thread-local: they are invisible to, and unaffected by, any other thread.
