@@ -1,4 +1,6 @@
-"""Generates tests/golden/reference_sam_decoder.npz by running the reference's own prompt encoder and mask decoder on the CPU:
+"""Generates tests/golden/reference_sam_decoder.npz (CASES) and tests/golden/reference_sam_decoder_edges.npz (EDGE_CASES: the tile,
+chunk and grid-limit edges, each recorded as a sample - edge_sample_index) by running the reference's own prompt encoder and mask
+decoder on the CPU:
 encoders/sam_encoder/segment_anything/modeling/{common,transformer,mask_decoder,prompt_encoder}.py, called as predictor.py:
 predict_torch calls them.  The four files need torch and numpy alone and are loaded by file under a synthetic package name (the
 package's own __init__ imports torchvision, which does not exist where this runs).
@@ -12,7 +14,8 @@ Per case:
   coords, labels, boxes    the prompts (absent where the case has none)
   sparse                   (B, T - 5, 256) float32: the reference's sparse prompt embeddings
   ref32, ref64             the logits (B, m, 4h, 4w) - for the 64 x 64 case `sample_idx` and the logits there (the first and last
-                           256 and 8192 drawn) - and iou32, iou64 (B, m)
+                           256 and 8192 drawn), for every edge case `sample_idx` and the logits there (all of up to 4096, else the
+                           first and last 256 and 1024 drawn) - and iou32, iou64 (B, m)
   gap, gap_iou             max |ref32 - ref64| over the WHOLE output; delta = 4 gap, delta_iou = 4 gap_iou (the project's
                            convention from the SAM mask vectors)
   nopen                    the logits with |ref64| <= delta (OPEN: their sign is not decided), of the whole output
@@ -22,7 +25,7 @@ is what it is, and the tests hold it to finiteness and its own delta only.
 
 Run it where the reference exists (the tests read only the npz):
 
-    python tests/golden/make_reference_sam_decoder_vectors.py
+    python tests/golden/make_reference_sam_decoder_vectors.py [--edges-only]
 """
 import importlib.util
 import os
@@ -56,7 +59,6 @@ def load_modeling():
 
 
 M = load_modeling()
-OUT = {}
 
 
 def build(case, weights):
@@ -72,7 +74,7 @@ def build(case, weights):
 
 
 @torch.no_grad()
-def record(case, seed):
+def record(case, seed, OUT, sample_index):
     weights = cases.make_weights(seed, case.qk_scale)
     features = torch.from_numpy(cases.make_features(case, seed))[None]
     coords, labels, boxes = cases.make_prompts(case, seed)
@@ -105,7 +107,7 @@ def record(case, seed):
             OUT[pre + k] = v
     OUT[pre + "sparse"] = sparse.numpy()
     if case.sampled:
-        idx = cases.sample_index(l32.size)
+        idx = sample_index(l32.size)
         OUT[pre + "sample_idx"], OUT[pre + "ref32"], OUT[pre + "ref64"] = idx, l32.reshape(-1)[idx], l64.reshape(-1)[idx]
     else:
         OUT[pre + "ref32"], OUT[pre + "ref64"] = l32, l64
@@ -117,16 +119,24 @@ def record(case, seed):
     return True
 
 
-def main():
-    for case in cases.CASES:
+def write(file, case_list, sample_index):
+    OUT = {}
+    for case in case_list:
         seed = cases.SEED
-        while not record(case, seed):
+        while not record(case, seed, OUT, sample_index):
             seed += 1
             assert seed < cases.SEED + 20, f"{case.name}: no seed found"
-    path = os.path.join(HERE, "reference_sam_decoder.npz")
+    path = os.path.join(HERE, file)
     np.savez_compressed(path, **OUT)
     print(f"wrote {path} ({os.path.getsize(path)} bytes)")
     assert os.path.getsize(path) < 1 << 20
+
+
+def main():
+    assert len(cases.CASES) == cases.N_CASES and all(c.sampled for c in cases.EDGE_CASES)
+    if "--edges-only" not in sys.argv:
+        write("reference_sam_decoder.npz", cases.CASES, cases.sample_index)
+    write("reference_sam_decoder_edges.npz", cases.EDGE_CASES, cases.edge_sample_index)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,8 @@ of size 4; at 0.25 the gap is 2e-5 .. 2e-4 and the prompts still give clearly di
 
 Features.  numpy.random.default_rng([seed, h, w]).standard_normal((256, h, w)) x feature_scale (0.5; 32 in the sharp case), float32.
 
-Prompts.  numpy.random.default_rng([seed, 77, case index]): coordinates uniform in the input image, then the boxes, float32.
+Prompts.  numpy.random.default_rng([seed, 77, case index]): coordinates uniform in the input image, then the boxes, float32.  The
+index is the case's place in CASES; the edge cases (EDGE_CASES) continue after it from N_CASES.
 """
 import numpy as np
 
@@ -47,6 +48,35 @@ CASES = [
     Case("sharp", (8, 5), 2, labels=[1, 0], input_size=(128, 80), sharp=True),
 ]
 BY_NAME = {c.name: c for c in CASES}
+
+# the edges of the two partitions of the hw image tokens (csrc/sam_decoder.hip): 32-token tiles (rows past hw are zeros in LDS, masked
+# in the token -> image softmax, guarded at the stores) and 256-token chunks of the token -> image attention (one running max / sum /
+# accumulator each, joined by the combine kernel).  Each case is the smallest grid that reaches its edge:
+#   e4x8          32: exactly one full tile, no masked row            e3x11      33: a tile plus one row
+#   e15x17       255: a chunk less one, the last tile has 31 rows     e16x16    256: exactly one chunk; B T = 32, one full row tile of the linear
+#   e1x257, e257x1    a second chunk of ONE token, h = 1 / w = 1 (4-float logit rows)
+#   e16x17       272: the second chunk is half a tile (thread-half 1 fully masked there)
+#   e18x16       288: the second chunk is one full tile, then the early break out of the tile loop
+#   e17x31       527: three chunks, 15 tokens in the last             e16x17_sharp   scores beyond 88 across two chunks
+#   e128x128   16384: the grid limit, 64 chunks
+# They live in their own golden file (reference_sam_decoder_edges.npz), every one as a sample (edge_sample_index).
+N_CASES = 8                       # len(CASES), frozen: the edge cases' prompt streams continue after it whatever either list becomes
+EDGE_CASES = [
+    Case("e4x8", (4, 8), 2, labels=[1], sampled=True),
+    Case("e3x11", (3, 11), 1, box=True, multimask=False, sampled=True),
+    Case("e15x17", (15, 17), 2, labels=[1, 0], sampled=True),
+    Case("e16x16", (16, 16), 2, labels=[1, 0, 1, 1, 0, -1, 1, 0, 1], box=True, sampled=True),
+    Case("e1x257", (1, 257), 2, labels=[0], multimask=False, sampled=True),
+    Case("e257x1", (257, 1), 1, labels=[1], sampled=True),
+    Case("e16x17", (16, 17), 3, labels=[1, 0, -1], sampled=True),
+    Case("e18x16", (18, 16), 1, box=True, sampled=True),
+    Case("e17x31", (17, 31), 2, labels=[1, 0], sampled=True),
+    Case("e16x17_sharp", (16, 17), 2, labels=[1, 0], sharp=True, sampled=True),
+    Case("e128x128", (128, 128), 1, labels=[1], sampled=True),
+]
+EDGE_BY_NAME = {c.name: c for c in EDGE_CASES}
+_PROMPT_STREAM = {c.name: i for i, c in enumerate(CASES)}
+_PROMPT_STREAM.update({c.name: N_CASES + i for i, c in enumerate(EDGE_CASES)})
 
 
 def _kind(name, shape):
@@ -87,7 +117,7 @@ def make_features(case, seed=SEED):
 def make_prompts(case, seed=SEED):
     """(coords (B, n, 2) float32 or None, labels (B, n) int32 or None, boxes (B, 4) float32 or None); prompt b's labels are the
     case's rolled by b, so that the prompts of a batch differ in more than their coordinates."""
-    rng = np.random.default_rng([seed, 77, [c.name for c in CASES].index(case.name)])
+    rng = np.random.default_rng([seed, 77, _PROMPT_STREAM[case.name]])
     ih, iw = case.input_size
     coords = labels = boxes = None
     if case.n_points:
@@ -103,3 +133,11 @@ def sample_index(size):
     """the 64 x 64 case records a fixed sample instead of its whole output: the first and last 256 logits and 8192 drawn"""
     rng = np.random.default_rng(7)
     return np.unique(np.concatenate([np.arange(256), size - 1 - np.arange(256), rng.integers(0, size, 8192)]))
+
+
+def edge_sample_index(size):
+    """every edge case records a sample: all of an output of up to 4096 logits, otherwise the first and last 256 and 1024 drawn"""
+    if size <= 4096:
+        return np.arange(size)
+    rng = np.random.default_rng(11)
+    return np.unique(np.concatenate([np.arange(256), size - 1 - np.arange(256), rng.integers(0, size, 1024)]))

@@ -1,7 +1,7 @@
 """CPU checks of the SAM decoder's test apparatus and of sam_decoder.py's surface (no GPU): the independent oracle
-(tests/sam_decoder_oracle.py) against the reference's recorded float64 results (tests/golden/reference_sam_decoder.npz), its
-prompt encoding against the reference's recorded sparse embeddings, and the errors the Python layer raises before any device
-work."""
+(tests/sam_decoder_oracle.py) against the reference's recorded float64 results (tests/golden/reference_sam_decoder.npz and, for
+the tile / chunk / grid-limit edge cases, reference_sam_decoder_edges.npz), its prompt encoding against the reference's recorded
+sparse embeddings, that the edge list reaches the edges it names, and the errors the Python layer raises before any device work."""
 import os
 
 import numpy as np
@@ -13,19 +13,24 @@ import sam_decoder_oracle as oracle
 from util import ROOT
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_sam_decoder.npz")
+EDGES = os.path.join(ROOT, "tests", "golden", "reference_sam_decoder_edges.npz")
 NAMES = [c.name for c in cases.CASES]
+EDGE_NAMES = [c.name for c in cases.EDGE_CASES]
+ALL = {**cases.BY_NAME, **cases.EDGE_BY_NAME}
 _Z, _W = {}, {}
 
 
 def golden():
+    """both golden files under one dict (the case names are disjoint)"""
     if not _Z:
         _Z.update(np.load(GOLDEN))
+        _Z.update(np.load(EDGES))
     return _Z
 
 
 def weights_of(name):
     """the case's weights by its recorded seed (made once per (seed, scale), left unchanged)"""
-    c = cases.BY_NAME[name]
+    c = ALL[name]
     key = (int(golden()[f"{name}/params"][8]), c.qk_scale)
     if key not in _W:
         _W[key] = cases.make_weights(*key)
@@ -58,9 +63,59 @@ def test_golden_file_matches_the_recipe():
     assert max(c.tokens for c in cases.CASES) == 16 and min(c.tokens for c in cases.CASES) == 7
 
 
-@pytest.mark.parametrize("name", NAMES)
+def test_edge_golden_file_matches_the_recipe():
+    z = golden()
+    assert len(cases.CASES) == cases.N_CASES and not set(cases.BY_NAME) & set(cases.EDGE_BY_NAME)
+    assert sorted({k.split("/")[0] for k in np.load(EDGES).files}) == sorted(EDGE_NAMES)
+    for c in cases.EDGE_CASES:
+        h, w, B, n, box, multi, ih, iw, seed, sharp = z[f"{c.name}/params"].tolist()
+        assert ((h, w), B, n, bool(box), bool(multi), (ih, iw), bool(sharp)) == (c.grid, c.B, c.n_points, c.box, c.multimask, c.input_size, c.sharp)
+        assert c.input_size == (16 * h, 16 * w) and c.sampled
+        coords, labels, boxes = cases.make_prompts(c, seed)
+        for got, want in zip(prompts_of(c.name), (coords, labels, boxes)):
+            assert (got is None) == (want is None) and (got is None or np.array_equal(got, want))
+        assert z[f"{c.name}/sparse"].shape == (c.B, c.tokens - 5, 256)
+        size = c.B * c.n_masks * 16 * h * w
+        idx = z[f"{c.name}/sample_idx"]
+        assert np.array_equal(idx, cases.edge_sample_index(size)) and (len(idx) == size if size <= 4096 else len(idx) <= 1536)
+        assert z[f"{c.name}/ref64"].shape == z[f"{c.name}/ref32"].shape == idx.shape and z[f"{c.name}/iou64"].shape == (c.B, c.n_masks)
+        assert float(z[f"{c.name}/delta"]) == 4 * float(z[f"{c.name}/gap"]) > 0
+        assert float(z[f"{c.name}/delta_iou"]) == 4 * float(z[f"{c.name}/gap_iou"]) > 0
+        if not c.sharp:
+            assert int(z[f"{c.name}/nopen"]) <= 0.001 * size
+    # the prompt streams continue after CASES': no edge case draws the prompts of another case
+    streams = [cases._PROMPT_STREAM[n] for n in NAMES + EDGE_NAMES]
+    assert streams == list(range(cases.N_CASES + len(EDGE_NAMES)))
+
+
+def test_edge_cases_reach_the_edges_they_name():
+    """computed from `grid` alone (csrc/sam_decoder.hip: 32-token tiles, CHUNK = 256 tokens per workgroup of the token -> image
+    attention), so that an edit of the list cannot silently drop an edge"""
+    TILE, CHUNK = 32, 256
+    reach = {}
+    for c in cases.EDGE_CASES:
+        hw = c.grid[0] * c.grid[1]
+        nch = -(-hw // CHUNK)
+        reach[c.name] = (hw, hw % TILE, nch, hw - (nch - 1) * CHUNK)          # tokens, of the last tile (0: full), chunks, tokens of the last chunk
+    assert reach == {"e4x8": (32, 0, 1, 32), "e3x11": (33, 1, 1, 33), "e15x17": (255, 31, 1, 255), "e16x16": (256, 0, 1, 256),
+                     "e1x257": (257, 1, 2, 1), "e257x1": (257, 1, 2, 1), "e16x17": (272, 16, 2, 16), "e18x16": (288, 0, 2, 32),
+                     "e17x31": (527, 15, 3, 15), "e16x17_sharp": (272, 16, 2, 16), "e128x128": (16384, 0, 64, 256)}
+    assert {r[1] for r in reach.values()} >= {0, 1, 15, 16, 31}
+    assert {r[2] for r in reach.values()} >= {1, 2, 3, 64}
+    last = {r[3] for r in reach.values() if r[2] > 1}
+    assert 1 in last and 32 in last and any(1 < n <= 16 for n in last)      # one token; one full tile then the break; thread-half 1 all masked
+    assert any(r[2] == 1 and r[3] == CHUNK for r in reach.values()) and any(r[2] == 1 and r[3] == CHUNK - 1 for r in reach.values())
+    multi = [c for c in cases.EDGE_CASES if -(-c.grid[0] * c.grid[1] // CHUNK) > 1]
+    assert any(c.sharp for c in multi) and any(c.grid[0] == 1 for c in multi) and any(c.grid[1] == 1 for c in multi)
+    import sam_decoder
+    assert max(r[0] for r in reach.values()) == sam_decoder.MAX_GRID and max(c.tokens for c in cases.EDGE_CASES) == sam_decoder.MAX_TOKENS
+    assert any(c.B * c.tokens == TILE for c in cases.EDGE_CASES)             # one full row tile of the token-side linear
+    assert {c.multimask for c in cases.EDGE_CASES} == {True, False}
+
+
+@pytest.mark.parametrize("name", NAMES + EDGE_NAMES)
 def test_oracle_prompt_encoding_against_the_reference(name):
-    c = cases.BY_NAME[name]
+    c = ALL[name]
     coords, labels, boxes = prompts_of(name)
     got = oracle.sparse_tokens(oracle.as_torch(weights_of(name)), coords, labels, boxes, c.input_size).numpy()
     want = golden()[f"{name}/sparse"]
@@ -68,10 +123,11 @@ def test_oracle_prompt_encoding_against_the_reference(name):
     assert np.abs(got - want).max() <= 1e-6
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + EDGE_NAMES)
 def test_oracle_float64_against_the_reference(name):
-    """fed the reference's recorded float32 prompt tokens, the oracle's float64 chain is the reference's float64 chain"""
-    z, c = golden(), cases.BY_NAME[name]
+    """fed the reference's recorded float32 prompt tokens, the oracle's float64 chain is the reference's float64 chain (at the
+    sample where a case records one: that is what entitles the GPU tests to judge whole tensors against the oracle)"""
+    z, c = golden(), ALL[name]
     seed = int(z[f"{name}/params"][8])
     low, iou, _ = oracle.decode(weights_of(name), cases.make_features(c, seed), z[f"{name}/sparse"], c.multimask, torch.float64)
     low, iou = low.numpy(), iou.numpy()
